@@ -27,6 +27,8 @@ stops the job with "rank r stalled in phase p".
 
 Extras (not the metric): --fused-normal (the fused A'A kernel), --lsqr K (K LSQR iterations on b = A x_true), --check (team
 mode: replicas bit-identical, adjoint against the fp64 sum of the members' partial sums; --dump FILE saves member 0's result).
+--dump-outputs DIR: after the timed steps, what the last one computed -- forward_d.npy (the range vector; rank 0's rows) and
+adjoint_mt.npy (the domain vector) -- at most 48 MiB in all: a vector over its share is a fixed, seeded sample (dump_outputs).
 BENCH_FORCE_DIST=1 under torch.distributed.run with one process exercises the RCCL path on a one-GPU box.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
@@ -99,7 +101,42 @@ def parse_args():
                     help="N > 1: one worker process per GPU (ranks), ONE worker driving all GPUs (team), or ranks with a team fallback (auto)")
     ap.add_argument("--check", action="store_true", help="team mode: verify replicas and the adjoint after the timed region (extra field)")
     ap.add_argument("--dump", type=str, default="", help="team mode: save member 0's adjoint result to this .npy file")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed (forward d, adjoint mt; rank / member 0) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 48 << 20     # --dump-outputs: at most this many bytes in all (the headline's d is 64 GiB, mt 64 MiB)
+DUMP_CHUNK = 4096                # a vector over its share is sampled in runs of this many consecutive elements ...
+DUMP_SEED = 20240601             # ... at positions drawn from this seed: the same positions in every run of the same arguments
+
+
+def dump_outputs(dirpath: str, outputs: dict) -> dict:
+    """--dump-outputs: the device vectors in `outputs` (name -> vector) as DIR/<name>.npy, in their own element type (float32 here).
+    A vector that fits its share of DUMP_BUDGET_BYTES is written whole; a larger one as a fixed sample: DUMP_CHUNK-element runs
+    starting at sorted, seeded multiples of DUMP_CHUNK.  Returns what was written, for the JSON line."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(outputs)
+    written = {}
+    for i, (name, x) in enumerate(outputs.items()):
+        total, item = len(x), x.dtype.itemsize
+        if x.dtype not in (np.float32, np.float64):
+            raise SystemExit(f"bench.py: --dump-outputs writes float32 / float64, {name} is {x.dtype}")
+        if total * item <= share:
+            host, how = x._download(), "whole"
+        else:
+            runs = min(total // DUMP_CHUNK, share // (DUMP_CHUNK * item))
+            starts = np.sort(np.random.default_rng(DUMP_SEED + i).choice(total // DUMP_CHUNK, size=runs, replace=False)) * DUMP_CHUNK
+            host = np.concatenate([x._download(int(s0), DUMP_CHUNK) for s0 in starts])
+            how = f"{runs} runs of {DUMP_CHUNK} consecutive elements at seeded positions (numpy default_rng({DUMP_SEED + i}))"
+        np.save(os.path.join(dirpath, name + ".npy"), host)
+        written[name] = {"elements": int(host.size), "of": int(total), "dtype": str(host.dtype), "sample": how}
+    return written
 
 
 # ---- heartbeats: a worker appends "<unix time> <phase>" lines to its file; the supervisor reads the last one -------------
@@ -702,6 +739,12 @@ def worker_ranks(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # ---- --dump-outputs: the last timed step's results, before the sections below reuse d and mt (rank 0: its own rows of d)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, {"forward_d": d, "adjoint_mt": mt})}
+        beat("outputs-dumped")
+
     # ---- multi-rank diagnostics, OUTSIDE the timed region: per-rank device times, the local adjoint kernel alone and the
     # stand-alone all-reduce, so that the exposed part of the exchange can be read off the line (adj_ms - adj_kernel_ms)
     multi = None
@@ -957,6 +1000,8 @@ def worker_ranks(args):
             "kernels": kernels,
         }
         out.update(extra)
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if placement_none is not None:
             out["placement_none"] = placement_none
         if world > 1:
@@ -1089,6 +1134,10 @@ def worker_team(args):
     team.synchronize()
     elapsed = time.perf_counter() - t0
     beat("timed-region-done")
+    dumped = None
+    if args.dump_outputs:                                                # member 0's results of the last timed step, before anything reuses them
+        dumped = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, {"forward_d": d[0], "adjoint_mt": mt[0]})}
+        beat("outputs-dumped")
 
     # outside the timed region: what ONE pair costs this host thread to enqueue (no synchronisation inside the bracket).  All N
     # members' launches come from here, so this must stay well below the pair's device time (projected 5.7 ms at 8 GPUs) --
@@ -1206,6 +1255,8 @@ def worker_team(args):
     if one_device and N > 1:
         out["valid_scaling_point"] = False                                # N members time-slicing one GPU
     out.update(extra)
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     out.update(launch_note("team: one process, one context per GPU (jh_comm_init_all)"))
     out["launch_mode"] = "team: one process, one context per GPU (jh_comm_init_all)"
     out["multi_gpu"] = multi
