@@ -382,6 +382,17 @@ typedef struct {
 int jh_chain_create(const jh_blockop *op, int type, int npre, const jh_chain_stage *pre, int nmid, const jh_chain_stage *mid, int npost,
                     const jh_chain_stage *post, jh_chain **out);
 int jh_chain_apply(const jh_chain *chain, jh_bvec *out, const jh_bvec *x, int accumulate);
+/* jh_chain_apply_range: the ADJOINT or NORMAL chain over the domain's elements [first_elem, first_elem + count) -- the weighted normal equations
+ * (JetComposite_df! / df'! over (A', W, A), src/Jets.jl:530-540) of a row partition, where the domain vector is summed over the ranks
+ * (1034-1057 on each rank's rows) and a finished range is all-reduced (jh_comm_allreduce_sum_range) under the next range's kernel.  Writes
+ * out[first_elem, first_elem + count) and nothing else, with the values jh_chain_apply writes there; `accumulate` as in jh_chain_apply.
+ * Bounds in elements (a complex element counts once) on 16-byte boundaries, except that the last range may end with the vector; count == 0 is
+ * a no-op.  Each range is launched as a vector of its own length: where the many-small-rows split walk cuts the rows into a different number of
+ * parts than the whole-vector call, tolerance parity; with jh_tune_set("adj_split", 0), or wherever both walk the rows in one part, the bits are
+ * jh_chain_apply's.  Counter "last_adj_parts" is the call's.  JH_ERR_INVALID: bounds outside the vector or off the 16-byte grid.
+ * JH_ERR_UNSUPPORTED: a FORWARD chain (it needs no exchange), or the operator was pointed again since the chain's row table was built and
+ * the library stream is capturing (the table's copy to the device would be captured; apply once outside the capture). */
+int jh_chain_apply_range(const jh_chain *chain, jh_bvec *out, const jh_bvec *x, int accumulate, int64_t first_elem, int64_t count);
 int jh_chain_destroy(jh_chain *chain);
 
 /* Fused solver updates (the two halves of an LSQR / CGLS iteration; callers: IterativeSolvers-style loops over

@@ -163,6 +163,7 @@ SYMBOLS = {
     "jh_blocksum_mul_adj_typed": (_int, [_int, _vpp, _dblp, C.POINTER(C.c_int32), _dblp, _vp, _vp]),
     "jh_chain_create": (_int, [_vp, _int, _int, C.POINTER(ChainStage), _int, C.POINTER(ChainStage), _int, C.POINTER(ChainStage), _vpp]),
     "jh_chain_apply": (_int, [_vp, _vp, _vp, _int]),
+    "jh_chain_apply_range": (_int, [_vp, _vp, _vp, _int, _i64, _i64]),
     "jh_chain_destroy": (_int, [_vp]),
     "jh_blockop_mul_axpby": (_int, [_vp, _vp, _vp, C.c_double, C.c_double, _dblp]),
     "jh_blockop_mul_adj_axpby": (_int, [_vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _dblp]),

@@ -230,19 +230,26 @@ def _native_cgnr_team(eng, b, x0, damp, atol, btol, maxiter, force_maxiter):
 
 def cgnr_core(eng, b, x0, damp, atol, btol, maxiter, force_maxiter=False) -> LsqrResult:
     """The same recurrences on an engine: the normal operator as A then A' (two passes and a range-sized temporary -- operators without
-    the fused kernel)."""
+    the fused kernel).  An engine with a `normal(y, p)` hook (y = A'A p in one pass, returns <p, A'A p> taken on the replicated domain vector:
+    a weighted row-partitioned shard's NORMAL chain, lsqr._ShardEngine) applies the normal operator through it instead, with no range vector."""
+    normal = getattr(eng, "normal", None)
     x = eng.zeros_dom() if x0 is None else eng.copy(eng.zeros_dom(), x0)
     bnorm = eng.norm_rng(b)
-    s, p, y, q = eng.zeros_dom(), eng.zeros_dom(), eng.zeros_dom(), eng.zeros_rng()
+    s, p, y = eng.zeros_dom(), eng.zeros_dom(), eng.zeros_dom()
+    q = eng.zeros_rng() if normal is None else None
     eng.adj(s, b, 1.0, 0.0)                                                 # s = A'b
     phi = bnorm * bnorm                                                     # ||r||^2 + damp^2 ||x||^2, by recurrence
     if x0 is not None:
-        qn = eng.fwd(q, x, 1.0, 0.0)                                         # A x0
-        eng.adj(y, q, 1.0, 0.0)                                             # A'A x0
+        if normal is None:
+            qn = eng.fwd(q, x, 1.0, 0.0)                                     # A x0
+            eng.adj(y, q, 1.0, 0.0)                                         # A'A x0
+            xax = qn * qn
+        else:
+            xax = normal(y, x)                                              # A'A x0, <x0, A'A x0>
         from .arrays import dot
 
         xb = dot(x[0], s[0]) if hasattr(x, "members") else dot(x, s)
-        phi = phi - 2.0 * float(getattr(xb, "real", xb)) + qn * qn + (damp * eng.norm_dom(x)) ** 2
+        phi = phi - 2.0 * float(getattr(xb, "real", xb)) + xax + (damp * eng.norm_dom(x)) ** 2
         eng.lincomb(s, [1.0, -1.0], [s, y])
         if damp:
             eng.lincomb(s, [1.0, -damp * damp], [s, x])
@@ -253,9 +260,12 @@ def cgnr_core(eng, b, x0, damp, atol, btol, maxiter, force_maxiter=False) -> Lsq
     if gamma > 0:
         while itn < maxiter:
             itn += 1
-            qn = eng.fwd(q, p, 1.0, 0.0)                                     # q = A p ; <p, A'A p> = ||q||^2
-            eng.adj(y, q, 1.0, 0.0)                                         # y = A'A p
-            delta = qn * qn + (damp * eng.norm_dom(p)) ** 2
+            if normal is None:
+                qn = eng.fwd(q, p, 1.0, 0.0)                                 # q = A p ; <p, A'A p> = ||q||^2
+                eng.adj(y, q, 1.0, 0.0)                                     # y = A'A p
+                delta = qn * qn + (damp * eng.norm_dom(p)) ** 2
+            else:
+                delta = normal(y, p) + (damp * eng.norm_dom(p)) ** 2        # y = A'A p in one pass ; <p, y>
             if damp:
                 eng.lincomb(y, [1.0, damp * damp], [y, p])
             if not (delta > 0 and math.isfinite(delta)):

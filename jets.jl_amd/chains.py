@@ -30,7 +30,8 @@ from .jets import JopLn, JopNl, JopAdjoint, Jop, domain, range_, mul_, adjoint
 MAX_STAGES = 4          # per side (jh_tall_chain.hip: JH_CHAIN_MAX_STAGES)
 _UNSUPPORTED = 4        # JH_ERR_UNSUPPORTED
 ENABLED = [True]        # tests / A-B timings: [False] sends every composite and sum down the stage-by-stage path of rounds 1-5
-STATS = {"chain_calls": 0, "sum_terms_fused": 0, "bcast_calls": 0}   # how often a fused run was applied (tests assert that the fused path is the one that ran)
+STATS = {"chain_calls": 0, "sum_terms_fused": 0, "bcast_calls": 0,    # how often a fused run was applied (tests assert that the fused path is the one that ran)
+         "chain_range_calls": 0}                                      # ... and how often one ran on an element range of the domain (rowpart's pipelined exchange)
 
 
 # ------------------------------------------------------------------------------ classification -----
@@ -203,6 +204,12 @@ class ChainHandle:
 
     def apply(self, out, x, accumulate: int = 0):
         check(lib.jh_chain_apply(self._h, out.handle, x.handle, accumulate))
+        return out
+
+    def apply_range(self, out, x, first: int, count: int, accumulate: int = 0):
+        """The ADJOINT / NORMAL chain on the domain's elements [first, first + count) (jh_chain_apply_range): out's other elements stay as they are."""
+        check(lib.jh_chain_apply_range(self._h, out.handle, x.handle, accumulate, int(first), int(count)))
+        STATS["chain_range_calls"] += 1
         return out
 
     def close(self):
@@ -429,6 +436,26 @@ def _chain_handle(cache: ChainCache | None, ctype, tall, pre, mid, post):
 
     h = cache.handle(key, make) if cache is not None else make()
     return None if h == "unsupported" else h
+
+
+def stages_of(op: Jop):
+    """The stages of a linear operator in application order, as JetComposite_df! applies them (src/Jets.jl:530-534): a composite's
+    operators right to left (an adjointed composite's are reversed and adjointed, jops_comp), anything else as one stage."""
+    return [(JopLn(o), range_(JopLn(o))) for o in reversed(_j.jops_comp(op))]
+
+
+def one_run(stages: Sequence, cache: ChainCache, tag, ctype: int, make: bool = True):
+    """When the WHOLE stage list is one fused run of chain type `ctype`: its ChainHandle (make=True; None when the library declines) or True
+    (make=False: planned, no handle built).  None otherwise."""
+    if not ENABLED[0]:
+        return None
+    steps = plan(stages, cache, tag)
+    if len(steps) != 1 or steps[0][0] != "chain" or steps[0][1] != ctype:
+        return None
+    if not make:
+        return True
+    _, ctype, tall, pre, mid, post, _members = steps[0]
+    return _chain_handle(cache, ctype, tall, pre, mid, post)
 
 
 def has_chain(steps) -> bool:

@@ -4,8 +4,9 @@
 #include "jh_tall_chain_kernels.h"
 
 namespace jhb {
-int chain_launch_adjoint(const jh_chain *ch, void *out, const void *in, int accumulate);   // jh_tall_chain_adj.hip
-int chain_launch_normal(const jh_chain *ch, void *out, const void *in, int accumulate);    // jh_tall_chain_nrm.hip
+// the domain's elements [first_elem, end_elem) (not scalars: a complex element counts once)
+int chain_launch_adjoint(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem);   // jh_tall_chain_adj.hip
+int chain_launch_normal(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem);    // jh_tall_chain_nrm.hip
 }  // namespace jhb
 
 namespace {
@@ -67,6 +68,26 @@ int chain_sync_rows(jh_chain *ch)
     JH_CHECK_HIP(hipMemcpyAsync(ch->dev_tab, ch->host_tab.data(), ch->host_tab.size() * sizeof(uint64_t), hipMemcpyHostToDevice, jh_ctx().stream));
     JH_CHECK_HIP(hipStreamSynchronize(jh_ctx().stream));
     ch->op_gen = op->table_gen;
+    return JH_OK;
+}
+
+// the checks every application of a chain makes (whole-vector or ranged): arguments, lengths, aliasing, the linearisation point, alignment
+int chain_check(const jh_chain *ch, const jh_bvec *out, const jh_bvec *x, int accumulate, const char *fn)
+{
+    const jh_blockop *op = ch->op;
+    JH_REQUIRE(accumulate >= -2 && accumulate <= 2, "%s: accumulate must be 0, +-1 or +-2 (got %d)", fn, accumulate);
+    JH_REQUIRE(out->dtype == op->dtype && x->dtype == op->dtype, "%s: dtype mismatch", fn);
+    const int64_t nrange = op->row_off[(size_t)op->nrow], ndom = op->col_off[(size_t)op->ncol];
+    const int64_t want_out = ch->type == JH_CHAIN_FORWARD ? nrange : ndom, want_in = ch->type == JH_CHAIN_ADJOINT ? nrange : ndom;
+    JH_REQUIRE(out->length == want_out && x->length == want_in, "%s: vectors have %lld / %lld elements, the chain maps %lld -> %lld", fn,
+               (long long)out->length, (long long)x->length, (long long)want_in, (long long)want_out);
+    JH_REQUIRE(out->data != x->data, "%s: the output must not alias the input", fn);
+    if (op->nonlinear && !op->pointed)
+        return jh_fail(JH_ERR_STATE, "%s: operator has nonlinear blocks and no linearisation point (jh_blockop_point)", fn);
+    const void *rng = ch->type == JH_CHAIN_FORWARD ? out->data : (ch->type == JH_CHAIN_ADJOINT ? x->data : nullptr);
+    const void *dom = ch->type == JH_CHAIN_FORWARD ? x->data : out->data;
+    if (!jhb::tall_unaligned_ok(op, rng, dom) || (ch->type == JH_CHAIN_NORMAL && !jhb::tall_unaligned_ok(op, nullptr, x->data)))
+        return jh_fail(JH_ERR_UNSUPPORTED, "%s: a vector or coefficient array is not aligned like its scalar", fn);
     return JH_OK;
 }
 
@@ -145,23 +166,11 @@ int jh_chain_apply(const jh_chain *ch, jh_bvec *out, const jh_bvec *x, int accum
     JH_REQUIRE(ch && out && x, "jh_chain_apply: null argument");
     const jh_blockop *op = ch->op;
     JH_TRY(jh_enter(op, out, x));
-    JH_REQUIRE(accumulate >= -2 && accumulate <= 2, "jh_chain_apply: accumulate must be 0, +-1 or +-2 (got %d)", accumulate);
-    JH_REQUIRE(out->dtype == op->dtype && x->dtype == op->dtype, "jh_chain_apply: dtype mismatch");
-    const int64_t nrange = op->row_off[(size_t)op->nrow], ndom = op->col_off[(size_t)op->ncol];
-    const int64_t want_out = ch->type == JH_CHAIN_FORWARD ? nrange : ndom, want_in = ch->type == JH_CHAIN_ADJOINT ? nrange : ndom;
-    JH_REQUIRE(out->length == want_out && x->length == want_in, "jh_chain_apply: vectors have %lld / %lld elements, the chain maps %lld -> %lld",
-               (long long)out->length, (long long)x->length, (long long)want_in, (long long)want_out);
-    JH_REQUIRE(out->data != x->data, "jh_chain_apply: the output must not alias the input");
-    if (op->nonlinear && !op->pointed)
-        return jh_fail(JH_ERR_STATE, "jh_chain_apply: operator has nonlinear blocks and no linearisation point (jh_blockop_point)");
-    const void *rng = ch->type == JH_CHAIN_FORWARD ? out->data : (ch->type == JH_CHAIN_ADJOINT ? x->data : nullptr);
-    const void *dom = ch->type == JH_CHAIN_FORWARD ? x->data : out->data;
-    if (!jhb::tall_unaligned_ok(op, rng, dom) || (ch->type == JH_CHAIN_NORMAL && !jhb::tall_unaligned_ok(op, nullptr, x->data)))
-        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_apply: a vector or coefficient array is not aligned like its scalar");
+    JH_TRY(chain_check(ch, out, x, accumulate, "jh_chain_apply"));
     if (ch->op_gen != op->table_gen) JH_TRY(chain_sync_rows(const_cast<jh_chain *>(ch)));   // (the operator was pointed again: its SQUARE rows' arrays moved)
     const int64_t n = op->row_len[0];
-    if (ch->type == JH_CHAIN_ADJOINT) return jhb::chain_launch_adjoint(ch, out->data, x->data, accumulate);
-    if (ch->type == JH_CHAIN_NORMAL) return jhb::chain_launch_normal(ch, out->data, x->data, accumulate);
+    if (ch->type == JH_CHAIN_ADJOINT) return jhb::chain_launch_adjoint(ch, out->data, x->data, accumulate, 0, out->length);
+    if (ch->type == JH_CHAIN_NORMAL) return jhb::chain_launch_normal(ch, out->data, x->data, accumulate, 0, out->length);
 #define JH_CHAIN_CALL(S, E, NS) launch_chain_fwd<S, E, NS>(ch, out->data, x->data, n * E, accumulate)
     switch (op->dtype) {
     case JH_F32: return JH_CHAIN_CALL(float, 1, 4);
@@ -171,6 +180,34 @@ int jh_chain_apply(const jh_chain *ch, jh_bvec *out, const jh_bvec *x, int accum
     }
 #undef JH_CHAIN_CALL
     return jh_fail(JH_ERR_INVALID, "jh_chain_apply: unknown dtype %d", op->dtype);
+}
+
+// The ADJOINT / NORMAL chain over the domain's elements [first_elem, first_elem + count): what a host pipelining the exchange of the domain vector range
+// by range against the kernels runs (weighted normal equations over a row partition, src/Jets.jl:530-540 over 1034-1057 summed across the ranks).  Writes
+// out[first_elem, first_elem + count) and nothing else: each domain element depends on the same element of x (NORMAL) or of every row of x (ADJOINT).
+int jh_chain_apply_range(const jh_chain *ch, jh_bvec *out, const jh_bvec *x, int accumulate, int64_t first_elem, int64_t count)
+{
+    JH_REQUIRE(ch && out && x, "jh_chain_apply_range: null argument");
+    const jh_blockop *op = ch->op;
+    JH_TRY(jh_enter(op, out, x));
+    if (ch->type == JH_CHAIN_FORWARD)
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_apply_range: a FORWARD chain needs no exchange (each rank's rows depend on the replicated domain vector alone)");
+    JH_TRY(chain_check(ch, out, x, accumulate, "jh_chain_apply_range"));
+    JH_REQUIRE(first_elem >= 0 && count >= 0 && first_elem <= out->length - count,
+               "jh_chain_apply_range: elements [%lld, %lld) outside the domain vector (%lld elements)", (long long)first_elem,
+               (long long)(first_elem + count), (long long)out->length);
+    const int64_t es = (int64_t)jh_dtype_size(op->dtype);
+    JH_REQUIRE((first_elem * es) % 16 == 0 && ((count * es) % 16 == 0 || first_elem + count == out->length),
+               "jh_chain_apply_range: range boundaries must be 16-byte aligned (the last range may end with the vector)");
+    if (count == 0) return JH_OK;
+    if (ch->op_gen != op->table_gen) {
+        // the row table is copied to the device and the stream synchronised: not inside a capture (the whole-vector call keeps doing it)
+        if (jhb::stream_is_capturing(jh_ctx().stream))
+            return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_apply_range: the operator was pointed again since the chain's row table was built, and the stream is capturing");
+        JH_TRY(chain_sync_rows(const_cast<jh_chain *>(ch)));
+    }
+    if (ch->type == JH_CHAIN_ADJOINT) return jhb::chain_launch_adjoint(ch, out->data, x->data, accumulate, first_elem, first_elem + count);
+    return jhb::chain_launch_normal(ch, out->data, x->data, accumulate, first_elem, first_elem + count);
 }
 
 }  // extern "C"
@@ -208,6 +245,7 @@ int bare_chain(const jh_blockop *op, void *out, const void *in, int mode, bool *
         }
     }
     *took = true;
-    return mode ? chain_launch_normal(slot, out, in, 0) : chain_launch_adjoint(slot, out, in, 0);
+    const int64_t ndom = op->col_off[(size_t)op->ncol];
+    return mode ? chain_launch_normal(slot, out, in, 0, 0, ndom) : chain_launch_adjoint(slot, out, in, 0, 0, ndom);
 }
 }  // namespace jhb

@@ -245,18 +245,21 @@ __global__ __launch_bounds__(BLK) void k_chain_fwd(const jh_dev_block *__restric
 // next DEPTH rows' table records already requested.
 template <typename S, int E, int NS, int U, int DEPTH, bool NT, int MODE, int BLK, int NW>
 __global__ __launch_bounds__(BLK) void k_chain_adj(const jh_dev_block *__restrict__ blocks, int64_t nrow, const ChainArgs ca, S *__restrict__ out,
-                                                   const S *__restrict__ in, int64_t n_scalars, int accumulate, int64_t rows_per_part, S *__restrict__ part_out)
+                                                   const S *__restrict__ in, int64_t n_scalars, int64_t s_begin, int64_t s_end, int accumulate,
+                                                   int64_t rows_per_part, S *__restrict__ part_out)
 {
+    // n_scalars: a row's length (the range vector's row stride); the launch covers the domain's scalars [s_begin, s_end) -- the whole vector, or one
+    // range of jh_chain_apply_range when the exchange is pipelined range by range (the bounds of k_tall_diag_adj, jh_tall.hip)
     typedef typename vec_of<S, NS>::type V;
     constexpr int NWA = NW > 0 ? NW : 1, RW = 1 + NW;
-    const int64_t s0 = ((int64_t)blockIdx.x * U * BLK + threadIdx.x) * NS;
+    const int64_t s0 = s_begin + ((int64_t)blockIdx.x * U * BLK + threadIdx.x) * NS;
     bool ok[U];
     int64_t sk[U];
     V acc[U], mv[U];
 #pragma unroll
     for (int k = 0; k < U; k++) {
-        ok[k] = (s0 + (int64_t)k * BLK * NS) < n_scalars;
-        sk[k] = pack_start<NS>(ok[k] ? s0 + (int64_t)k * BLK * NS : 0, n_scalars);
+        ok[k] = (s0 + (int64_t)k * BLK * NS) < s_end;
+        sk[k] = pack_start<NS>(ok[k] ? s0 + (int64_t)k * BLK * NS : s_begin, s_end);   // (a range shorter than one pack ends with the vector: loaded from s_end - NS)
         acc[k] = (V)(S)0;                                                               // m .= 0 (1042)
         if (MODE == 1) mv[k] = ldu<false, S, NS>(in + sk[k]);
     }
@@ -330,7 +333,7 @@ __global__ __launch_bounds__(BLK) void k_chain_adj(const jh_dev_block *__restric
             }
     };
     // split-row walk (many rows of small blocks, jh_tall.hip: pick_adj_parts): workgroup row blockIdx.y sums rows [y, y + 1) * rows_per_part in order into slab y
-    // of part_out (n_scalars apart); the fold and the list after A' follow in launches of their own
+    // of part_out (s_end - s_begin apart, scalar s at s - s_begin); the fold and the list after A' follow in launches of their own
     int64_t i = 0;
     if (part_out) {
         i = (int64_t)blockIdx.y * rows_per_part;
@@ -364,7 +367,7 @@ __global__ __launch_bounds__(BLK) void k_chain_adj(const jh_dev_block *__restric
         batch(i, e, std::integral_constant<int, 1>{});
     }
     if (part_out) {
-        S *slab = part_out + (int64_t)blockIdx.y * n_scalars;
+        S *slab = part_out + (int64_t)blockIdx.y * (s_end - s_begin) - s_begin;
 #pragma unroll
         for (int k = 0; k < U; k++)
             if (ok[k]) st_pack<false, S, NS>(slab, s0 + (int64_t)k * BLK * NS, sk[k], acc[k]);
@@ -380,13 +383,14 @@ __global__ __launch_bounds__(BLK) void k_chain_adj(const jh_dev_block *__restric
 }
 
 // The split walk's last step when the chain goes on after A' (or accumulates into what `out` holds): out = accumulate(out, Q(folded)).
+// `folded` is addressed like `out` (scalar s at folded + s); the launch covers [s_begin, s_end)
 template <typename S, int E, int NS>
-__global__ __launch_bounds__(256) void k_chain_finish(const ChainArgs ca, S *__restrict__ out, const S *__restrict__ folded, int64_t n_scalars, int accumulate)
+__global__ __launch_bounds__(256) void k_chain_finish(const ChainArgs ca, S *__restrict__ out, const S *__restrict__ folded, int64_t s_begin, int64_t s_end, int accumulate)
 {
     typedef typename vec_of<S, NS>::type V;
-    const int64_t s = ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;
-    if (s >= n_scalars) return;
-    const int64_t sc = pack_start<NS>(s, n_scalars);
+    const int64_t s = s_begin + ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;
+    if (s >= s_end) return;
+    const int64_t sc = pack_start<NS>(s, s_end);
     const bool rmw = accumulate == 1 || accumulate == -1;
     const V found = rmw ? ldu<false, S, NS>(out + sc) : (V)(S)0;
     const V r = dom_prog<S, E, NS, V>(ca.post, ca.post_c[0], ca.post_c[1], ldu<false, S, NS>(folded + sc), sc);
@@ -441,12 +445,19 @@ int launch_chain_fwd(const jh_chain *ch, void *d, const void *m, int64_t n_scala
     return JH_OK;
 }
 
+// The domain's scalars [s_begin, s_end): the whole vector (jh_chain_apply) or one range of it (jh_chain_apply_range).  A range is launched like a
+// whole vector of its length -- shape, grid and split-walk parts from the RANGE's pack count, as launch_tall_adj_u does -- so where the whole-vector
+// call and a range both walk the rows in one part they have the same bits (every scalar is its own ordered row sum); where the part counts differ
+// (many rows of small blocks: pick_adj_parts) the fold adds different partial sums -- tolerance parity, DESIGN.md section 3.  The nontemporal choice
+// stays the whole application's: a range's coefficients come back one application later, after every other range's.
 template <typename S, int E, int NS, int MODE>
-int launch_chain_adj(const jh_chain *ch, void *out, const void *in, int64_t n_scalars, int accumulate)
+int launch_chain_adj(const jh_chain *ch, void *out, const void *in, int64_t n_scalars, int accumulate, int64_t s_begin, int64_t s_end)
 {
     jh_context &c = jh_ctx();
     const jh_blockop *op = ch->op;
-    const int64_t packs = (n_scalars + NS - 1) / NS;
+    const int64_t span = s_end - s_begin;
+    if (span <= 0) return JH_OK;
+    const int64_t packs = (span + NS - 1) / NS;
     const int64_t row_bytes = n_scalars * (int64_t)sizeof(S);
     const bool off_grid = row_bytes % 16 != 0 || !op->coeff_aligned16 || !ch->coeff16 || ((((uintptr_t)out) | ((uintptr_t)in)) & 15u) != 0;
     const double streamed = ch->stream_bytes + (MODE == 0 ? (double)op->nrow * (double)row_bytes : 0.0);
@@ -464,24 +475,24 @@ int launch_chain_adj(const jh_chain *ch, void *out, const void *in, int64_t n_sc
     // many rows of small blocks: the split-row walk (jh_tall.hip: pick_adj_parts; adj_split = 0 keeps the ordered, bit-exact walk) -- parts of the row sum into
     // slabs of the scratch buffer, the fold of k_fold_parts, then the stages after A' and the accumulation on the folded vector (k_chain_finish; folded
     // straight into `out` when there is neither).  Tolerance parity, like every split walk.
-    int64_t parts = n_scalars < NS ? 1 : jhb::pick_adj_parts(gx, op->nrow), rows_per_part = 0;
+    int64_t parts = span < NS ? 1 : jhb::pick_adj_parts(gx, op->nrow), rows_per_part = 0;   // (a range shorter than one pack loads from before s_begin: one part)
     // (one workgroup per CU, up to two: the chain's three or four streams per row leave the ordered walk latency-bound there -- 4096 x 64^3, 256 workgroups:
     // A' o W o A 4.37 TB/s in one part, 7.04 in two, 6.3 in four or more; profiles/bench_chains_r06_split.txt)
-    if (parts == 1 && c.adj_split < 0 && n_scalars >= NS && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
+    if (parts == 1 && c.adj_split < 0 && span >= NS && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
     const bool finish = accumulate != 0 || (ch->args.post.st[0] & 15u) != CK_NONE;
     S *slabs = nullptr, *folded = (S *)out;
     if (parts > 1) {
         rows_per_part = (op->nrow + parts - 1) / parts;
         parts = (op->nrow + rows_per_part - 1) / rows_per_part;
         void *sp = nullptr;
-        JH_TRY(jhb::split_slabs(out, (size_t)(parts + (finish ? 1 : 0)) * (size_t)n_scalars * sizeof(S), &sp));
+        JH_TRY(jhb::split_slabs(out, (size_t)(parts + (finish ? 1 : 0)) * (size_t)span * sizeof(S), &sp));
         slabs = (S *)sp;
-        if (finish) folded = slabs + parts * n_scalars;
+        if (finish) folded = slabs + parts * span - s_begin;                                    // (addressed like `out`: scalar s at folded + s)
     }
     c.last_adj_parts = parts;
 #define JH_CHAIN_ADJ(BLKV, UV, DV, NTV, NWV)                                                                                                 \
     hipLaunchKernelGGL((k_chain_adj<S, E, NS, UV, DV, NTV, MODE, BLKV, NWV>), dim3((unsigned)gx, (unsigned)parts), dim3(BLKV), 0, c.stream, op->dev_blocks, \
-                       op->nrow, ch->args, (S *)out, (const S *)in, n_scalars, accumulate, rows_per_part, slabs)
+                       op->nrow, ch->args, (S *)out, (const S *)in, n_scalars, s_begin, s_end, accumulate, rows_per_part, slabs)
 #define JH_CHAIN_ADJ_NW(BLKV, UV, DV, NTV)                                                                                                    \
     switch (ch->nw) {                                                                                                                      \
     case 0: JH_CHAIN_ADJ(BLKV, UV, DV, NTV, 0); break;                                                                                     \
@@ -500,10 +511,10 @@ int launch_chain_adj(const jh_chain *ch, void *out, const void *in, int64_t n_sc
 #undef JH_CHAIN_ADJ
     JH_CHECK_HIP(hipGetLastError());
     if (parts > 1) {
-        JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, n_scalars, parts, folded, 0, n_scalars));
+        JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, span, parts, folded, s_begin, s_end));
         if (finish) {
             hipLaunchKernelGGL((k_chain_finish<S, E, NS>), dim3((unsigned)((packs + 255) / 256)), dim3(256), 0, c.stream, ch->args, (S *)out, (const S *)folded,
-                               n_scalars, accumulate);
+                               s_begin, s_end, accumulate);
             JH_CHECK_HIP(hipGetLastError());
         }
     }

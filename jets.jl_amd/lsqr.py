@@ -24,7 +24,7 @@ import math
 import os
 
 from ._ffi import lib, check, JetsHipError
-from .arrays import zeros, lincomb_, norm, copyto_, reshape, fill_
+from .arrays import zeros, lincomb_, norm, dot, copyto_, reshape, fill_
 
 
 def _plain(coefs):
@@ -175,6 +175,15 @@ class _ShardEngine(_Engine):
         super().__init__(shard.local_op)
         self.shard = shard
         self.force_collective = os.environ.get("BENCH_FORCE_DIST", "0") == "1"   # run the exchange even with one rank (validation)
+        if getattr(shard, "fused_normal", False):
+            self.normal = self._normal                   # a weighted shard: cgnr_core applies L'L as one NORMAL chain + a pipelined exchange
+
+    def _normal(self, y, p) -> float:
+        """y = L'L p summed over the ranks (rowpart: normal_mul_, one fused pass + the ranged all-reduces); returns <p, y>, taken on the
+        replicated domain vector (every rank the same value)."""
+        self.shard.normal_mul_(y, p, force_collective=self.force_collective)
+        v = dot(p, y)
+        return float(getattr(v, "real", v))
 
     def norm_rng(self, x) -> float:
         return self.shard.norm_range(x, 2)
@@ -198,7 +207,7 @@ class _ShardEngine(_Engine):
     def adj(self, v, u, alpha, beta) -> float:
         if self._tmp_d is None:
             self._tmp_d = zeros(_j.domain(self.A))
-        self.shard.mul_adj_(self._tmp_d, u)              # local A'u + all-reduce
+        self.shard.mul_adj_(self._tmp_d, u, force_collective=self.force_collective)   # local A'u + all-reduce (pipelined where the shard can)
         lincomb_(v, _plain([alpha, beta]), [self._tmp_d, v])
         return float(norm(v))
 

@@ -11,7 +11,7 @@ the domain vector after the local adjoint, and scalar all-reduces for range-side
 The summation order across ranks differs from the sequential reference => tolerance parity at
 world_size > 1 (bit-exact at world_size 1).
 
-The compute engine is injected (`local_mul`, `local_mul_adj`, `as_tensor`) so the sharding and
+The compute engine is injected (`local_mul`, `local_mul_adj`, `local_normal`, `as_tensor`) so the sharding and
 collective logic can be exercised with world_size-2 gloo tests on CPU against a test double; the
 product wiring (`for_device`) uses the HIP path only.
 """
@@ -152,21 +152,39 @@ class RowPartitionedOp:
 
     def __init__(self, part: RowPartition, local_op, comm: Comm, local_mul: Callable, local_mul_adj: Callable,
                  local_dot: Callable, local_norm: Callable, pipelined_adj: Callable | None = None,
-                 pipelined_step: Callable | None = None, pipelined_normal: Callable | None = None):
+                 pipelined_step: Callable | None = None, pipelined_normal: Callable | None = None,
+                 local_normal: Callable | None = None, chains=None):
         self.part, self.local_op, self.comm = part, local_op, comm
         self._mul, self._mul_adj, self._dot, self._norm = local_mul, local_mul_adj, local_dot, local_norm
         self._pipelined_adj = pipelined_adj   # optional: local adjoint and all-reduce pipelined chunk by chunk
         self._pipelined_step = pipelined_step  # optional: one-pass Golub-Kahan step, its w all-reduced chunk by chunk
         self._pipelined_normal = pipelined_normal  # optional: the fused A'A, its result all-reduced chunk by chunk
+        self._local_normal = local_normal      # optional: this rank's L'L m in one fused pass (a weighted shard's NORMAL chain), no range temporary
+        self._chains = chains                  # the device handles a weighted shard's routes hold (released by close())
+
+    @property
+    def fused_normal(self) -> bool:
+        """normal_mul_ needs no range temporary: a weighted shard (L = W_loc o A_loc, ...) applies L'L as one fused NORMAL chain."""
+        return self._local_normal is not None
+
+    def close(self):
+        """Release the chain handles of a weighted shard (the operator itself stays the caller's)."""
+        if self._chains is not None:
+            self._chains.close()
 
     def normal_mul_(self, y, m, tmp_local=None, force_collective: bool = False):
         """y = (A'A) m = sum over ALL rows A_i'(A_i m)  (JetComposite_df! over (A', A), src/Jets.jl:530-534, on a row partition): every
         rank's fused A_k'A_k m -- its coefficients read once, no range-side intermediate -- in element ranges
         (jh_blockop_normal_mul_range), the all-reduce of a finished range under the next range's kernel.  Operators without the
-        fused kernel run forward then adjoint through `tmp_local` (a range vector of this rank's rows)."""
+        fused kernel run forward then adjoint through `tmp_local` (a range vector of this rank's rows).  A weighted shard (L = W_loc o A_loc,
+        a * (W o A), W o A o M: one fused run of the chain planner) runs L'L = A'W'WA as ONE NORMAL chain per range (jh_chain_apply_range), exchanged
+        the same way -- or, unpipelined, the whole-vector NORMAL chain and one all-reduce; it needs no `tmp_local`."""
         if self._pipelined_normal is not None and (self.comm.world > 1 or force_collective):
             if self._pipelined_normal(y, self.local_op, m):
                 return y
+        if tmp_local is None and self._local_normal is not None:
+            self._local_normal(y, self.local_op, m)
+            return self.comm.all_reduce_sum_(y, force=force_collective)
         if tmp_local is None:
             raise ValueError("normal_mul_: this operator has no fused A'A; pass tmp_local (a range vector of this rank's rows)")
         self.mul_(tmp_local, m)
@@ -213,6 +231,72 @@ class RowPartitionedOp:
         return self.comm.all_reduce_scalars([float(self._norm(x_local, p)) ** p], "sum")[0] ** (1.0 / p)
 
 
+class _ShardChains:
+    """The fused chains of a WEIGHTED shard: a local operator L that the chain planner (chains.py) turns into one run around the shard's
+    tall operator -- W_loc o A_loc (W_loc = JopDiagonal of this rank's rows of the weights), a block-diagonal @blockop of weights o A_loc,
+    W o A o M, a * (W o A).  adjoint(L) is one ADJOINT chain, adjoint(L) o L one NORMAL chain (W' and W read one coefficient stream:
+    jh_chain_create's dedupe).  Planned here once; the handles live in this object's cache until close().  A bare block operator is not
+    weighted: plain shards keep their routes (jh_blockop_*_range)."""
+
+    def __init__(self, L):
+        from . import chains as _chn
+        from . import jetblock as _blk
+        from .jets import JopLn, JopAdjoint, adjoint, compose, jops_comp
+
+        self._chn = _chn
+        self.cache = _chn.ChainCache()
+        self._adj = self._nrm = self._nrm_op = None
+        if isinstance(L, (JopLn, JopAdjoint)) and not _blk.isblockop(L) and len(jops_comp(L)) >= 2:
+            self._nrm_op = compose(adjoint(L), L)
+            self._adj = _chn.stages_of(adjoint(L))
+            self._nrm = _chn.stages_of(self._nrm_op)
+        self.has_adj = self._adj is not None and _chn.one_run(self._adj, self.cache, "rowpart_adj", _chn.CHAIN_ADJOINT, make=False) is not None
+        self.has_normal = self._nrm is not None and _chn.one_run(self._nrm, self.cache, "rowpart_normal", _chn.CHAIN_NORMAL, make=False) is not None
+
+    def adjoint(self):
+        """The ChainHandle of adjoint(L), or None (not one run; the library declined)."""
+        return self._chn.one_run(self._adj, self.cache, "rowpart_adj", self._chn.CHAIN_ADJOINT) if self.has_adj else None
+
+    def normal(self):
+        return self._chn.one_run(self._nrm, self.cache, "rowpart_normal", self._chn.CHAIN_NORMAL) if self.has_normal else None
+
+    def local_normal(self, y, L, m):
+        """y = L'L m on this rank's rows: the whole-vector NORMAL chain (the stage-by-stage chain when the library declines it)."""
+        from .jets import mul_
+
+        h = self.normal()
+        if h is None:
+            return mul_(y, self._nrm_op, m)
+        h.apply(y, m)
+        self._chn.STATS["chain_calls"] += 1
+        return y
+
+    def close(self):
+        self.cache.close()
+
+
+def _ranged_chain(h, out, x, nchunks: int, enqueue_exchange, join) -> bool:
+    """A weighted shard's chain in `nchunks` element ranges (jh_chain_apply_range, accumulate 0: with +-1 every rank would add `out` once), the
+    exchange of a finished range enqueued behind its kernel.  False when there is no handle, or the library declines before anything was
+    enqueued (the caller then takes today's route)."""
+    from ._ffi import JetsHipError
+
+    if h is None:
+        return False
+    done = 0
+    try:
+        for lo, cnt in _chunk_bounds(out.length(), nchunks):
+            h.apply_range(out, x, lo, cnt, 0)
+            enqueue_exchange(lo, cnt)
+            done += 1
+    except JetsHipError as e:
+        if e.status == 4 and done == 0:                       # JH_ERR_UNSUPPORTED before anything was enqueued
+            return False
+        raise
+    join()
+    return True
+
+
 def for_device(part: RowPartition, local_op, comm=None) -> RowPartitionedOp:
     """Product wiring: HIP kernels for the local work, RCCL for the exchange -- through torch.distributed's "nccl"
     backend (default; the all-reduce is ordered against the library's HIP stream with torch.cuda.ExternalStream)
@@ -224,7 +308,9 @@ def for_device(part: RowPartition, local_op, comm=None) -> RowPartitionedOp:
     if comm is not None:
         if isinstance(comm, AbiComm):
             return _for_device_abi(part, local_op, comm)
-        return RowPartitionedOp(part, local_op, comm, lambda d, A, m: mul_(d, A, m), lambda m, A, d: mul_(m, adjoint(A), d), dot, norm)
+        sc = _ShardChains(local_op)
+        return RowPartitionedOp(part, local_op, comm, lambda d, A, m: mul_(d, A, m), lambda m, A, d: mul_(m, adjoint(A), d), dot, norm,
+                                local_normal=sc.local_normal if sc.has_normal else None, chains=sc)
     import torch
 
     ext = torch.cuda.ExternalStream(_device.stream_handle(), device=torch.device("cuda", _device.init()))
@@ -277,13 +363,23 @@ def for_device(part: RowPartition, local_op, comm=None) -> RowPartitionedOp:
             for w in works:
                 w.wait()                                      # the library stream waits for every chunk's all-reduce
 
+    sc = _ShardChains(local_op)
+
+    def weighted(out, x, h) -> bool:
+        """A weighted shard's ADJOINT / NORMAL chain range by range, each range's all-reduce on RCCL's stream behind it."""
+        if nchunks <= 1 or not dist.is_initialized():
+            return False
+        t = tensor_of(out)
+        works = []
+        return _ranged_chain(h, out, x, nchunks, lambda lo, cnt: exchange(t, lo, cnt, works), lambda: join(works))
+
     def pipelined_adj(m, A, d) -> bool:
         """Local adjoint in `nchunks` element ranges (jh_blockop_mul_adj_range); the all-reduce of a finished range
         runs on RCCL's stream while the kernel of the next range runs on the library stream.  Same values as the
         unpipelined path.  Returns False when the operator has no ranged kernel (then the caller does it in one piece)."""
         nat = native_of(A)
         if nat is None:
-            return False
+            return A is local_op and sc.has_adj and weighted(m, d, sc.adjoint())
         t = tensor_of(m)
         works = []
         try:
@@ -301,7 +397,7 @@ def for_device(part: RowPartition, local_op, comm=None) -> RowPartitionedOp:
         """The fused A'A in `nchunks` element ranges (jh_blockop_normal_mul_range), exchanged like the adjoint's."""
         nat = native_of(A)
         if nat is None:
-            return False
+            return A is local_op and sc.has_normal and weighted(y, m, sc.normal())
         t = tensor_of(y)
         works = []
         try:
@@ -340,7 +436,8 @@ def for_device(part: RowPartition, local_op, comm=None) -> RowPartitionedOp:
         return out.value
 
     return RowPartitionedOp(part, local_op, comm, lambda d, A, m: mul_(d, A, m), lambda m, A, d: mul_(m, adjoint(A), d), dot, norm,
-                            pipelined_adj=pipelined_adj, pipelined_step=pipelined_step, pipelined_normal=pipelined_normal)
+                            pipelined_adj=pipelined_adj, pipelined_step=pipelined_step, pipelined_normal=pipelined_normal,
+                            local_normal=sc.local_normal if sc.has_normal else None, chains=sc)
 
 
 def _chunk_bounds(n: int, nchunks: int):
@@ -372,10 +469,19 @@ def _for_device_abi(part: RowPartition, local_op, comm: AbiComm) -> RowPartition
         jt = A.jet
         return _blk._native_op(jt.s.get("_native"), jt.s["ops"], jt.rng.eltype())
 
+    sc = _ShardChains(local_op)
+
+    def weighted(out, x, h) -> bool:
+        """A weighted shard's ADJOINT / NORMAL chain range by range, each range all-reduced on the communicator's stream behind it."""
+        if nchunks <= 1:
+            return False
+        return _ranged_chain(h, out, x, nchunks, lambda lo, cnt: check(lib.jh_comm_allreduce_sum_range(out.handle, lo, cnt)),
+                             lambda: check(lib.jh_comm_join()))
+
     def pipelined_adj(m, A, d) -> bool:
         nat = native_of(A)
         if nat is None:
-            return False
+            return A is local_op and sc.has_adj and weighted(m, d, sc.adjoint())
         done = 0
         try:
             for lo, cnt in _chunk_bounds(m.length(), nchunks):
@@ -392,7 +498,7 @@ def _for_device_abi(part: RowPartition, local_op, comm: AbiComm) -> RowPartition
     def pipelined_normal(y, A, m) -> bool:
         nat = native_of(A)
         if nat is None:
-            return False
+            return A is local_op and sc.has_normal and weighted(y, m, sc.normal())
         done = 0
         try:
             for lo, cnt in _chunk_bounds(y.length(), nchunks):
@@ -426,7 +532,8 @@ def _for_device_abi(part: RowPartition, local_op, comm: AbiComm) -> RowPartition
         return (out.value, True)
 
     return RowPartitionedOp(part, local_op, comm, lambda d, A, m: mul_(d, A, m), lambda m, A, d: mul_(m, adjoint(A), d), dot, norm,
-                            pipelined_adj=pipelined_adj, pipelined_step=pipelined_step, pipelined_normal=pipelined_normal)
+                            pipelined_adj=pipelined_adj, pipelined_step=pipelined_step, pipelined_normal=pipelined_normal,
+                            local_normal=sc.local_normal if sc.has_normal else None, chains=sc)
 
 
 # ------------------------------------------------------------------ ONE process, several contexts -------------------------

@@ -501,6 +501,11 @@ function _enter_context_of_coefficients(ops)
     end
 end
 
+# a never-reused serial per device operator (an address is reused once the operator is destroyed): what caches of things built on an operator key on
+const _op_serials = Dict{Ptr{Cvoid},Int}()
+const _op_serial_next = Ref(0)
+_op_serial(h::Ptr{Cvoid}) = get!(() -> (_op_serial_next[] += 1), _op_serials, h)
+
 function native_handle(ops::AbstractMatrix{<:Jop}, ::Type{T}) where {T}
     get!(_handles, ops) do
         descs = [block_desc(ops[i,j]) for i = 1:size(ops,1), j = 1:size(ops,2)]      # column-major == the C layout
@@ -851,13 +856,15 @@ function _chain_sides_ok(t, pre, mid, post)
     true
 end
 
-const _chain_handles = Dict{Any,Any}()          # signature -> (jh_chain* or C_NULL when the library declined, what the handle borrows)
+const _chain_handles = Dict{Any,Any}()          # signature (its operator by serial) -> (jh_chain* or C_NULL when the library declined, what the handle borrows)
+const _CHAIN_CACHE_MAX = 64                     # a composite built anew per application with fresh weights adds a handle each time: bounded
 _stage_sig(st) = st.kind === :scale ? (:s, st.a, st.flags) : (:d, UInt(_device_ptr(st.vec isa HipArray ? st.vec.slab : whole(st.vec))), length(st.vec), st.conj)
 
 function _chain_handle(ctype::Cint, t, pre, mid, post, ::Type{T}) where {T}
-    key = (ctype, t.h, map(_stage_sig, pre), map(_stage_sig, mid), map(_stage_sig, post))
+    key = (ctype, _op_serial(t.h), map(_stage_sig, pre), map(_stage_sig, mid), map(_stage_sig, post))
     hit = get(_chain_handles, key, nothing)
     hit === nothing || return hit[1]
+    length(_chain_handles) >= _CHAIN_CACHE_MAX && close_chains!()
     keep = Any[]
     function pack(sts, nptr)
         arr = jh_chain_stage[]
@@ -887,6 +894,14 @@ function close_chains!()                                                # releas
         h == C_NULL || ccall((:jh_chain_destroy, LIB), Cint, (Ptr{Cvoid},), h)
     end
     empty!(_chain_handles)
+end
+function _close_chains_of!(serial::Int)                                 # the chain handles built on ONE operator (release! before jh_blockop_destroy)
+    for key in [k for (k, _) in _chain_handles]
+        key[2] == serial || continue
+        h = _chain_handles[key][1]
+        h == C_NULL || ccall((:jh_chain_destroy, LIB), Cint, (Ptr{Cvoid},), h)
+        delete!(_chain_handles, key)
+    end
 end
 
 # x -> stages -> out with every fusable run in one ccall; false when nothing fuses (the caller runs the reference's chain).
@@ -1109,6 +1124,48 @@ function mul_adj_partitioned!(m::HipArray{T}, A::JopLn, d_local::BlockArray{T,<:
     end
     check(ccall((:jh_comm_join, LIB), Cint, ()))                           # the library stream waits for the exchange; no host sync
     m
+end
+# a WEIGHTED shard L = W_loc ∘ A_loc (or a ∘ W ∘ A, W ∘ A ∘ M: a composite that the chain planner makes ONE run around the shard's tall operator):
+# the chain of the stages `stages` (application order) in `chunks` element ranges (jh_chain_apply_range, accumulate 0 -- with ±1 every rank would add
+# `out` once), each range all-reduced on the communicator's stream behind its kernel; false when the stages are not one run of type `ctype` or the
+# library declines before anything was enqueued
+function _chain_partitioned!(out::HipArray{T}, x, stages::Vector, ctype::Cint, chunks::Integer) where {T}
+    (chunks <= 1 || handle(out) == C_NULL || handle(x) == C_NULL) && return false
+    st = Any[_chain_stage(op, T) for op in stages]
+    steps = _chain_segments(st)
+    (length(steps) == 1 && steps[1][1] === :chain && steps[1][2] == ctype) || return false
+    _, _, t, pre, mid, post, _, _ = steps[1]
+    _chain_sides_ok(t, pre, mid, post) || return false
+    h = _chain_handle(ctype, t, pre, mid, post, T)
+    h == C_NULL && return false
+    n = length(out)
+    step = cld(cld(n, chunks), 16384) * 16384                             # range bounds on 64 KiB boundaries
+    for lo = 0:step:n-1
+        cnt = min(step, n - lo)
+        status = ccall((:jh_chain_apply_range, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Int64, Int64), h, handle(out), handle(x), 0, lo, cnt)
+        (status == 4 && lo == 0) && return false
+        check(status)
+        check(ccall((:jh_comm_allreduce_sum_range, LIB), Cint, (Ptr{Cvoid}, Int64, Int64), handle(out), lo, cnt))
+    end
+    check(ccall((:jh_comm_join, LIB), Cint, ()))
+    true
+end
+_composite_ops(L::JopLn) = jet(L).f! === JetComposite_f! ? state(L).ops : nothing
+# m = L'd summed over the ranks for a weighted shard (src/Jets.jl:536-540 on this rank's rows, 1034-1057 across the ranks): the ADJOINT chain of L'
+# range by range; else the whole-vector adjoint and one all-reduce
+function mul_adj_weighted_partitioned!(m::HipArray{T}, L::JopLn, d_local::BlockArray{T,<:HipArray{T}}; chunks::Integer=4) where {T}
+    ops = _composite_ops(L)
+    ops !== nothing && _chain_partitioned!(m, d_local, _stages_df′(ops), Cint(1), chunks) && return m
+    mul!(m, L', d_local)
+    allreduce_sum!(m)
+end
+# y = L'L m summed over the ranks (530-540 over (L', L)): ONE pass of the NORMAL chain A'∘W'∘W∘A per range (W' and W read one coefficient stream),
+# no range-sized temporary; else the stage-by-stage chain and one all-reduce
+function normal_mul_weighted_partitioned!(y::HipArray{T}, L::JopLn, m::HipArray{T}; chunks::Integer=4) where {T}
+    ops = _composite_ops(L)
+    ops !== nothing && _chain_partitioned!(y, m, vcat(_stages_df(ops), _stages_df′(ops)), Cint(2), chunks) && return y
+    mul!(y, L' ∘ L, m)
+    allreduce_sum!(y)
 end
 # one Golub-Kahan step of a row-partitioned operator, pipelined the same way; returns the GLOBAL ||u|| (the one host sync)
 function bidiag_step_partitioned!(u::BlockArray{T,<:HipArray{T}}, w::HipArray{T}, A::JopLn, v::HipArray{T}, alpha::Real, beta::Real; chunks::Integer=4) where {T}
@@ -1401,7 +1458,11 @@ end
 function release!(ops)
     h = pop!(_handles, ops, C_NULL)
     delete!(_points, ops)
-    h == C_NULL || ccall((:jh_blockop_destroy, LIB), Cint, (Ptr{Cvoid},), h)
+    if h != C_NULL
+        serial = pop!(_op_serials, h, 0)
+        serial == 0 || _close_chains_of!(serial)                         # a chain borrows its operator: gone first
+        ccall((:jh_blockop_destroy, LIB), Cint, (Ptr{Cvoid},), h)
+    end
     nothing
 end
 function Base.close(j::Jet{D,R,typeof(JetBlock_f!)}) where {D<:JetAbstractSpace,R<:JetBSpace{<:Any,<:HipSpace}}
