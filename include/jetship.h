@@ -394,6 +394,20 @@ int jh_chain_apply(const jh_chain *chain, jh_bvec *out, const jh_bvec *x, int ac
  * the library stream is capturing (the table's copy to the device would be captured; apply once outside the capture). */
 int jh_chain_apply_range(const jh_chain *chain, jh_bvec *out, const jh_bvec *x, int accumulate, int64_t first_elem, int64_t count);
 int jh_chain_destroy(jh_chain *chain);
+/* One Golub-Kahan / LSQR step over a FORWARD chain L = R o A o P (weighted least squares: lsqr(W o A o M, b), docs/src/index.md:235-246;
+ * the composite applied as src/Jets.jl:530-540, the step as the solvers over vec(A) use it, 1138-1154) in ONE pass over A, the range-side
+ * weights and u:
+ *   t_i = R(a_i .* P(v)) ;  u_i <- alpha*t_i + beta*u_i ;  w = Q(sum_i conj(a_i) .* R^H(u_i)) ;  *normsq = ||u||^2
+ * with Q = P^H and R^H built from the handle's own stage lists (reversed, every diagonal conjugated; the same arrays, read once).  u and w are
+ * bit-identical to jh_chain_apply of the FORWARD chain into a temporary, `u .= alpha*tmp .+ beta*u` (beta == 0: u .= alpha*tmp, u not read)
+ * and the ADJOINT chain of L' -- where the many-small-rows split walk sums w in parts, tolerance parity as in jh_chain_apply (adj_split = 0:
+ * the bits).  ||u||^2 in fp64, per-workgroup partials folded in a fixed order; normsq NULL: not read back (no synchronisation).
+ * (3 + nw) N n s bytes (nw: the range-side coefficient arrays) against (8 + 2 nw) N n s for the chain into a temporary, the lincomb, the norm and
+ * the ADJOINT chain.  Counter
+ * "last_adj_parts" is the call's.  JH_ERR_INVALID: not a FORWARD chain, vectors of the wrong length or aliased.  JH_ERR_UNSUPPORTED before
+ * anything is touched: R and R^H together exceed 4 range-side stages (the caller keeps the chain-then-adjoint route), a vector not aligned like
+ * its scalar, or the operator was pointed again since the row table was built while the library stream is capturing. */
+int jh_chain_bidiag_step(const jh_chain *fwd, jh_bvec *u, const jh_bvec *v, jh_bvec *w, double alpha, double beta, double *normsq);
 
 /* Fused solver updates (the two halves of an LSQR / CGLS iteration; callers: IterativeSolvers-style loops over
  * vec(A), src/Jets.jl:1138-1154).  d = alpha*(A m) + beta*d  /  m = alpha*(A' d) + beta*m  with real alpha, beta,
@@ -493,6 +507,19 @@ int jh_cgnr_solve_partitioned(const jh_blockop *op, jh_bvec *b, jh_bvec *x, int 
                               int force_maxiter, jh_lsqr_result *res, double *history);
 int jh_cgnr_solve_team(int n, const jh_blockop *const *ops, jh_bvec *const *bs, jh_bvec *const *xs, int use_x0, double damp, double atol,
                        double btol, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history);
+/* The three solvers on a FORWARD chain L = R o A o P in place of the operator: min ||L x - b||_2 (+ damp^2 ||x||^2) for the weighted least
+ * squares users run as `lsqr(W o A o M, b)` (docs/src/index.md:235-246; the composite is src/Jets.jl:530-540, the solver loop over vec(L)
+ * 1138-1154).  Same arguments, recurrences, stopping rules and result records as jh_lsqr_solve / jh_cgls_solve / jh_cgnr_solve; one GPU, the
+ * host-driven loop at every size (the graph-replayed small-operator loops are for bare operators).  LSQR iterates on jh_chain_bidiag_step,
+ * (3 + nw) N n s bytes; CGLS on L'L (the NORMAL program pre P, mid R then R^H, post P^H derived from the same handle: (1 + nw) N n s) plus
+ * the step; CGNR on L'L alone.  The warm start u <- b - L x0 is one step with a scratch domain-sized w: no range-sized temporary.
+ * JH_ERR_UNSUPPORTED before anything is touched where jh_chain_bidiag_step declines (R + R^H above 4 stages): keep the generic loop. */
+int jh_lsqr_solve_chain(const jh_chain *fwd, jh_bvec *u, jh_bvec *x, int use_x0, double damp, double atol, double btol, double conlim,
+                        int maxiter, int force_maxiter, jh_lsqr_result *res, double *history);
+int jh_cgls_solve_chain(const jh_chain *fwd, jh_bvec *u, jh_bvec *x, int use_x0, double damp, double atol, double btol, int maxiter,
+                        int force_maxiter, jh_lsqr_result *res, double *history);
+int jh_cgnr_solve_chain(const jh_chain *fwd, jh_bvec *b, jh_bvec *x, int use_x0, double damp, double atol, double btol, int maxiter,
+                        int force_maxiter, jh_lsqr_result *res, double *history);
 /* ---------------------------------------------------------------- RCCL over xGMI ----------- */
 /* Row partition of a tall operator across the GPUs of a node (one process per GPU): the forward needs no exchange
  * (src/Jets.jl:1015-1031), the adjoint is a sum over rows (1045-1053) -> one in-place all-reduce of the domain vector

@@ -165,6 +165,7 @@ SYMBOLS = {
     "jh_chain_apply": (_int, [_vp, _vp, _vp, _int]),
     "jh_chain_apply_range": (_int, [_vp, _vp, _vp, _int, _i64, _i64]),
     "jh_chain_destroy": (_int, [_vp]),
+    "jh_chain_bidiag_step": (_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, _dblp]),
     "jh_blockop_mul_axpby": (_int, [_vp, _vp, _vp, C.c_double, C.c_double, _dblp]),
     "jh_blockop_mul_adj_axpby": (_int, [_vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _dblp]),
     "jh_blockop_mul_scaled": (_int, [_vp, _vp, _vp, C.c_double, _int]),
@@ -182,6 +183,9 @@ SYMBOLS = {
     "jh_cgnr_solve": (_int, [_vp, _vp, _vp, _int, C.c_double, C.c_double, C.c_double, _int, _int, C.POINTER(LsqrResultC), _dblp]),
     "jh_cgnr_solve_partitioned": (_int, [_vp, _vp, _vp, _int, C.c_double, C.c_double, C.c_double, _int, _int, C.POINTER(LsqrResultC), _dblp]),
     "jh_cgnr_solve_team": (_int, [_int, _vpp, _vpp, _vpp, _int, C.c_double, C.c_double, C.c_double, _int, _int, C.POINTER(LsqrResultC), _dblp]),
+    "jh_lsqr_solve_chain": (_int, [_vp, _vp, _vp, _int, C.c_double, C.c_double, C.c_double, C.c_double, _int, _int, C.POINTER(LsqrResultC), _dblp]),
+    "jh_cgls_solve_chain": (_int, [_vp, _vp, _vp, _int, C.c_double, C.c_double, C.c_double, _int, _int, C.POINTER(LsqrResultC), _dblp]),
+    "jh_cgnr_solve_chain": (_int, [_vp, _vp, _vp, _int, C.c_double, C.c_double, C.c_double, _int, _int, C.POINTER(LsqrResultC), _dblp]),
     "jh_team_mul": (_int, [_int, _vpp, _vpp, _vpp]),
     "jh_team_mul_adj": (_int, [_int, _vpp, _vpp, _vpp, _int]),
     "jh_team_normal_mul": (_int, [_int, _vpp, _vpp, _vpp, _int]),

@@ -20,7 +20,7 @@ import os
 from ._ffi import lib, check, JetsHipError
 from .arrays import reshape
 from . import jets as _j
-from .lsqr import LsqrResult, _Engine, _ShardEngine, _TeamEngine, _unwrap_vec
+from .lsqr import LsqrResult, _Engine, _ShardEngine, _TeamEngine, _unwrap_vec, _chain_of, _count_chain_solve
 
 __all__ = ["cgls", "cgls_core", "cgnr", "cgnr_core"]
 
@@ -60,7 +60,8 @@ def _native(eng, b, x0, damp, atol, btol, maxiter, overwrite_b, force_maxiter):
     from ._ffi import LsqrResultC
     from .rowpart import AbiComm
 
-    if os.environ.get("JETS_CGLS_NATIVE", "1") == "0" or eng.native is None:
+    chn = _chain_of(eng)
+    if os.environ.get("JETS_CGLS_NATIVE", "1") == "0" or (eng.native is None and chn is None):
         return None
     shard = getattr(eng, "shard", None)
     if shard is not None and not (isinstance(shard.comm, AbiComm) or shard.comm.world == 1):
@@ -70,13 +71,17 @@ def _native(eng, b, x0, damp, atol, btol, maxiter, overwrite_b, force_maxiter):
     res = LsqrResultC()
     hist = (C.c_double * builtins.max(2 * int(maxiter), 1))()
     try:
-        solve = lib.jh_cgls_solve_partitioned if shard is not None else lib.jh_cgls_solve
-        check(solve(eng.native.handle, u.handle, x.handle, 0 if x0 is None else 1, float(damp), float(atol), float(btol), int(maxiter),
+        if chn is not None:                                     # one FORWARD chain: its NORMAL program and one-pass step (jh_cgls_solve_chain)
+            solve, h = lib.jh_cgls_solve_chain, chn.fwd.handle
+        else:
+            solve, h = (lib.jh_cgls_solve_partitioned if shard is not None else lib.jh_cgls_solve), eng.native.handle
+        check(solve(h, u.handle, x.handle, 0 if x0 is None else 1, float(damp), float(atol), float(btol), int(maxiter),
                     1 if force_maxiter else 0, C.byref(res), hist))
     except JetsHipError as e:
         if e.status != 4:                                       # JH_ERR_UNSUPPORTED comes before anything is touched: the generic loop
             raise
         return None
+    _count_chain_solve(chn)
     return _result(x, res, hist)
 
 
@@ -184,11 +189,12 @@ def _native_cgnr(eng, b, x0, damp, atol, btol, maxiter, force_maxiter):
 
     shard = getattr(eng, "shard", None)
     nat = eng.native
-    if nat is None and shard is None and hasattr(eng, "A"):
+    chn = _chain_of(eng)
+    if nat is None and shard is None and chn is None and hasattr(eng, "A"):
         from . import jetblock as _blk
 
         nat = _blk._grid_native(eng.A)                 # round 6: N x (2 .. 4) grids of diagonals have a fused A'A too (jh_grid_normal.hip)
-    if os.environ.get("JETS_CGLS_NATIVE", "1") == "0" or nat is None:
+    if os.environ.get("JETS_CGLS_NATIVE", "1") == "0" or (nat is None and chn is None):
         return None
     if shard is not None and not (isinstance(shard.comm, AbiComm) or shard.comm.world == 1):
         return None
@@ -196,13 +202,17 @@ def _native_cgnr(eng, b, x0, damp, atol, btol, maxiter, force_maxiter):
     res = LsqrResultC()
     hist = (C.c_double * builtins.max(2 * int(maxiter), 1))()
     try:
-        solve = lib.jh_cgnr_solve_partitioned if shard is not None else lib.jh_cgnr_solve
-        check(solve(nat.handle, b.handle, x.handle, 0 if x0 is None else 1, float(damp), float(atol), float(btol), int(maxiter),
+        if chn is not None:                                     # one FORWARD chain: its NORMAL program (jh_cgnr_solve_chain)
+            solve, h = lib.jh_cgnr_solve_chain, chn.fwd.handle
+        else:
+            solve, h = (lib.jh_cgnr_solve_partitioned if shard is not None else lib.jh_cgnr_solve), nat.handle
+        check(solve(h, b.handle, x.handle, 0 if x0 is None else 1, float(damp), float(atol), float(btol), int(maxiter),
                     1 if force_maxiter else 0, C.byref(res), hist))
     except JetsHipError as e:
         if e.status != 4:
             raise
         return None
+    _count_chain_solve(chn)
     return _result(x, res, hist)
 
 

@@ -17,6 +17,7 @@ from __future__ import annotations
 import builtins
 import ctypes as C
 import itertools
+import os
 from typing import Sequence
 
 import numpy as np
@@ -31,7 +32,8 @@ MAX_STAGES = 4          # per side (jh_tall_chain.hip: JH_CHAIN_MAX_STAGES)
 _UNSUPPORTED = 4        # JH_ERR_UNSUPPORTED
 ENABLED = [True]        # tests / A-B timings: [False] sends every composite and sum down the stage-by-stage path of rounds 1-5
 STATS = {"chain_calls": 0, "sum_terms_fused": 0, "bcast_calls": 0,    # how often a fused run was applied (tests assert that the fused path is the one that ran)
-         "chain_range_calls": 0}                                      # ... and how often one ran on an element range of the domain (rowpart's pipelined exchange)
+         "chain_range_calls": 0,                                      # ... and how often one ran on an element range of the domain (rowpart's pipelined exchange)
+         "chain_step_calls": 0, "chain_solve_calls": 0}               # the solvers on a FORWARD chain: one-pass steps (jh_chain_bidiag_step), whole native solves (jh_*_solve_chain)
 
 
 # ------------------------------------------------------------------------------ classification -----
@@ -201,6 +203,10 @@ class ChainHandle:
 
         a_pre, a_mid, a_post = pack(pre, False), pack(mid, True), pack(post, False)
         check(lib.jh_chain_create(tall.nat.handle, ctype, len(pre), a_pre, len(mid), a_mid, len(post), a_post, C.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
 
     def apply(self, out, x, accumulate: int = 0):
         check(lib.jh_chain_apply(self._h, out.handle, x.handle, accumulate))
@@ -618,3 +624,54 @@ def try_sum(out, x, ops: Sequence[Jop], sgns: Sequence[str], transposed: bool, w
         return out
     finally:
         ws.release()
+
+
+# ------------------------------------------------------------------------------ the solvers on a chain ----
+class SolverChains:
+    """The fused routes of the one-GPU solvers (lsqr.py, cgls.py) on a composite L = R o A o P that the planner turns into ONE FORWARD run
+    (W o A, a block-diagonal @blockop of weights o A, W o A o M, a * (W o A)): `fwd` is its ChainHandle -- the Golub-Kahan step
+    (jh_chain_bidiag_step) and the native solves (jh_*_solve_chain) take it --, `normal()` the NORMAL chain of adjoint(L) o L (cgnr_core's hook).
+    fwd is None when L is not one such run, the library declines, or JETS_CHAIN_STEP=0 (today's route: the chain into a range temporary, then
+    the ADJOINT chain)."""
+
+    def __init__(self, L):
+        from . import jetblock as _blk
+
+        self.cache = ChainCache()
+        self.fwd = None
+        self._nrm = None
+        if os.environ.get("JETS_CHAIN_STEP", "1") == "0":
+            return
+        if isinstance(L, (JopLn, JopAdjoint)) and not _blk.isblockop(L) and len(_j.jops_comp(L)) >= 2:
+            h = one_run(stages_of(L), self.cache, "solver_fwd", CHAIN_FORWARD)
+            if isinstance(h, ChainHandle):
+                self.fwd = h
+                self._nrm = stages_of(_j.compose(adjoint(L), L))
+
+    def step(self, u, v, w, alpha: float, beta: float):
+        """u <- alpha L v + beta u ; w <- L'u ; returns ||u||^2, or None when the library declines (R and R^H above four stages: the caller
+        keeps the two halves)."""
+        out = C.c_double(0)
+        try:
+            check(lib.jh_chain_bidiag_step(self.fwd.handle, u.handle, v.handle, w.handle, float(alpha), float(beta), C.byref(out)))
+        except JetsHipError as e:
+            if e.status != _UNSUPPORTED:
+                raise
+            self.fwd = None
+            return None
+        STATS["chain_step_calls"] += 1
+        return out.value
+
+    def normal_planned(self) -> bool:
+        """Does adjoint(L) o L plan to ONE NORMAL run?  Planning only: the handle is built on the first normal() call."""
+        return self._nrm is not None and one_run(self._nrm, self.cache, "solver_normal", CHAIN_NORMAL, make=False) is not None
+
+    def normal(self):
+        """The ChainHandle of adjoint(L) o L (built on first use), or None."""
+        if self._nrm is None:
+            return None
+        h = one_run(self._nrm, self.cache, "solver_normal", CHAIN_NORMAL)
+        return h if isinstance(h, ChainHandle) else None
+
+    def close(self):
+        self.cache.close()

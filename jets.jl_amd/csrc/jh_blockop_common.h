@@ -180,6 +180,8 @@ int tall_fwd_mixed(const jh_blockop *op, void *d, const void *m, int fmode = 0);
 int tall_adj(const jh_blockop *op, void *out, const void *in, int mode, bool mixed, int64_t first_elem = 0, int64_t end_elem = -1);
 int fold_parts(int dtype, const void *parts, int64_t part_stride, int64_t nparts, void *out, int64_t s_begin, int64_t s_end);   // (scalars: a complex vector is 2n reals)
 int split_adjoint_tmp(const jh_blockop *op, void **tmp);
+// ---- jh_tall_step.hip
+int step_finish_normsq(int64_t nparts, double *normsq);   // fold ctx.part_dev[0 .. nparts) in a fixed order; normsq != NULL: read it back (synchronises)
 // ---- jh_general.hip
 int general_fwd(const jh_blockop *op, void *d, const void *m, int fmode = 0);
 int general_adj(const jh_blockop *op, void *m, const void *d);

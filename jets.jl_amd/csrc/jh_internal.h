@@ -165,6 +165,10 @@ jh_context &jh_ctx();                  // the calling thread's current context (
 // wrong for an operator that fits -- its coefficients would come from HBM every iteration although the cache could hold them.
 // Knob nt: 0 never, 2 always, 1 (default): nontemporal unless the working set of one pass is at most nt_resident_mib.
 namespace jhb { bool grid_normal_ok(const jh_blockop *op, const void *y, const void *m); }   // jh_grid_normal.hip
+namespace jhb {   // jh_tall_chain.hip: L' (JH_CHAIN_ADJOINT) / L'L (JH_CHAIN_NORMAL) of a FORWARD chain; the checks of the solvers on a chain (op: its operator)
+int chain_apply_derived(const jh_chain *fwd, int which, jh_bvec *out, const jh_bvec *in);
+int chain_solver_ok(const jh_chain *fwd, const jh_bvec *u, const jh_bvec *x, const jh_blockop **op);
+}
 inline bool jh_stream_nt(double working_set_bytes)
 {
     const jh_context &c = jh_ctx();

@@ -338,8 +338,40 @@ __global__ __launch_bounds__(256) void k_lsqr_xw_dev(S *v, S *x, S *w, int64_t n
 //          domain-side updates run redundantly on every member with the SAME host scalars, so the replicas stay bit-identical.
 enum class Exch { none, ranks, team };
 
+// The four passes the loops below take from a shard: a block operator's fused kernels, or (one GPU, jh_*_solve_chain) a FORWARD chain L = R o A o P
+// and the programs derived from it.  A chain has no forward-with-axpby of its own: the warm start u <- b - L x0 is one step into a scratch domain vector.
+struct Passes {
+    const jh_blockop *op = nullptr;
+    const jh_chain *ch = nullptr;
+    jh_bvec *scratch = nullptr;                  // (chain: the step's w of the warm start)
+    Passes() = default;
+    Passes(const Passes &) = delete;
+    Passes &operator=(const Passes &) = delete;
+    ~Passes() { if (scratch) (void)jh_bvec_destroy(scratch); }
+    // u <- a*(L x) + b*u, ||u||^2
+    int fwd_axpby(jh_bvec *u, const jh_bvec *x, double a, double b, double *normsq)
+    {
+        if (!ch) return jh_blockop_mul_axpby(op, u, x, a, b, normsq);
+        if (!scratch) {
+            const int64_t len1[1] = {x->length};
+            JH_TRY(jh_bvec_create(1, len1, x->dtype, &scratch));
+        }
+        return jh_chain_bidiag_step(ch, u, x, scratch, a, b, normsq);
+    }
+    // out = L' in
+    int adjoint(jh_bvec *out, const jh_bvec *in) { return ch ? jhb::chain_apply_derived(ch, JH_CHAIN_ADJOINT, out, in) : jh_blockop_mul_adj(op, out, in); }
+    // u <- a*(L v) + b*u ; w = L'u ; ||u||^2
+    int step(jh_bvec *u, const jh_bvec *v, jh_bvec *w, double a, double b, double *normsq)
+    {
+        return ch ? jh_chain_bidiag_step(ch, u, v, w, a, b, normsq) : jh_blockop_bidiag_step(op, u, v, w, a, b, normsq);
+    }
+    // y = L'L m
+    int normal(jh_bvec *y, const jh_bvec *m) { return ch ? jhb::chain_apply_derived(ch, JH_CHAIN_NORMAL, y, m) : jh_blockop_normal_mul(op, y, m); }
+};
+
 static int lsqr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *us, jh_bvec *const *xs, int use_x0, double damp, double atol,
-                     double btol, double conlim, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history, const Exch ex)
+                     double btol, double conlim, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history, const Exch ex,
+                     const jh_chain *ch = nullptr)
 {
     JH_REQUIRE(ops && us && xs && res && M >= 1, "jh_lsqr_solve: null argument");
     JH_REQUIRE(maxiter >= 0, "jh_lsqr_solve: maxiter must be >= 0");
@@ -353,9 +385,11 @@ static int lsqr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
         JH_REQUIRE(xs[k]->length == n && xs[k]->dtype == dtype, "jh_lsqr_solve: member %d's x differs in length or element type", k);
         // before anything is touched: the caller can still take another path.  Rows off the 16-byte pack grid are fine (jh_blockop_tall_step_ok): the
         // pipelined exchange cuts the DOMAIN at 16-byte bounds, and the last range may end with the vector
-        if (!jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data))
+        if (!ch && !jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data))
             return jh_fail(JH_ERR_UNSUPPORTED, "jh_lsqr_solve: needs a tall operator of >= 2 equal elementwise rows");
     }
+    std::vector<Passes> pass((size_t)M);
+    for (int k = 0; k < M; k++) { pass[k].op = ops[k]; pass[k].ch = ch; }
     std::vector<Tmp> t((size_t)M);
     const int64_t len1[1] = {n};
     const int64_t ns_dom = n * (jh_dtype_complex(dtype) ? 2 : 1);
@@ -407,13 +441,13 @@ static int lsqr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
     const double bnorm = std::sqrt(s2);
     double beta = bnorm;
     if (use_x0) {                                                        // u <- b - A x0
-        for (int k = 0; k < M; k++) JH_TRY(jh_blockop_mul_axpby(ops[k], us[k], xs[k], -1.0, 1.0, &locals[k]));
+        for (int k = 0; k < M; k++) JH_TRY(pass[k].fwd_axpby(us[k], xs[k], -1.0, 1.0, &locals[k]));
         JH_TRY(global_sum(locals, &s2));
         beta = std::sqrt(s2);
     }
     double alpha = 0.0;
     if (beta > 0) {                                                      // v = A'u / beta
-        for (int k = 0; k < M; k++) JH_TRY(jh_blockop_mul_adj(ops[k], t[k].atu, us[k]));
+        for (int k = 0; k < M; k++) JH_TRY(pass[k].adjoint(t[k].atu, us[k]));
         JH_TRY(exchange([&](int k) { return jh_comm_allreduce_sum(t[k].atu); }));
         for (int k = 0; k < M; k++) JH_TRY(lincomb1(t[k].v, 1.0 / beta, t[k].atu));
         JH_TRY(jh_norm(t[0].v, 2.0, &alpha));                            // replicas are identical: member 0 speaks for all
@@ -461,7 +495,7 @@ static int lsqr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
                     }
                 }
             } else {
-                JH_TRY(jh_blockop_bidiag_step(ops[0], us[0], t[0].v, t[0].atu, 1.0, -alpha / beta_prev, &s2));
+                JH_TRY(pass[0].step(us[0], t[0].v, t[0].atu, 1.0, -alpha / beta_prev, &s2));
             }
             beta = std::sqrt(s2);
             if (wnorm_pending) {                                         // the step's read-back synchronised member 0's stream: it has landed
@@ -807,7 +841,8 @@ extern "C" int jh_lsqr_solve_team(int n, const jh_blockop *const *ops, jh_bvec *
 // 4 N n s bytes per iteration against LSQR's 3 N n s.  Partitioned: the first pass needs a SCALAR exchange only (every shard's
 // <p, A_k'A_k p>), the second is LSQR's pipelined step (ranged all-reduces of A'r under the kernels, one host synchronisation).
 static int cgls_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *us, jh_bvec *const *xs, int use_x0, double damp, double atol,
-                     double btol, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history, const Exch ex)
+                     double btol, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history, const Exch ex,
+                     const jh_chain *ch = nullptr)
 {
     JH_REQUIRE(ops && us && xs && res && M >= 1, "jh_cgls_solve: null argument");
     JH_REQUIRE(maxiter >= 0, "jh_cgls_solve: maxiter must be >= 0");
@@ -820,9 +855,11 @@ static int cgls_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
     for (int k = 0; k < M; k++) {
         JH_REQUIRE(xs[k]->length == n && xs[k]->dtype == dtype, "jh_cgls_solve: member %d's x differs in length or element type", k);
         // before anything is touched (rows off the 16-byte pack grid too, as in lsqr_impl)
-        if (!jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data) || ops[k]->nrow < 2)
+        if (!ch && (!jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data) || ops[k]->nrow < 2))
             return jh_fail(JH_ERR_UNSUPPORTED, "jh_cgls_solve: needs a tall (>= 2 rows) operator of equal elementwise rows");
     }
+    std::vector<Passes> pass((size_t)M);
+    for (int k = 0; k < M; k++) { pass[k].op = ops[k]; pass[k].ch = ch; }
     struct Work {                                                         // domain-sized work vectors of one member
         jh_bvec *p = nullptr, *s = nullptr, *y = nullptr;
         ~Work()
@@ -887,10 +924,10 @@ static int cgls_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
     const double bnorm = std::sqrt(s2);
     double rr = s2;                                                       // ||r||^2
     if (use_x0) {                                                         // r <- b - A x0
-        for (int k = 0; k < M; k++) JH_TRY(jh_blockop_mul_axpby(ops[k], us[k], xs[k], -1.0, 1.0, &locals[k]));
+        for (int k = 0; k < M; k++) JH_TRY(pass[k].fwd_axpby(us[k], xs[k], -1.0, 1.0, &locals[k]));
         JH_TRY(global_sum(locals, &rr));
     }
-    for (int k = 0; k < M; k++) JH_TRY(jh_blockop_mul_adj(ops[k], t[k].s, us[k]));           // s = A'r
+    for (int k = 0; k < M; k++) JH_TRY(pass[k].adjoint(t[k].s, us[k]));                     // s = A'r
     JH_TRY(exchange([&](int k) { return jh_comm_allreduce_sum(t[k].s); }));
     double gamma = 0.0;
     JH_TRY(finish_s(&gamma));
@@ -915,7 +952,7 @@ static int cgls_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
             };
             for (int k = 0; k < M; k++) {
                 JH_TRY(stamp(k, 0));
-                JH_TRY(jh_blockop_normal_mul(ops[k], t[k].y, t[k].p));
+                JH_TRY(pass[k].normal(t[k].y, t[k].p));
                 JH_TRY(jh_dot_begin(t[k].p, t[k].y));
                 JH_TRY(stamp(k, 1));
             }
@@ -970,7 +1007,7 @@ static int cgls_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
                     }
                 }
             } else {
-                JH_TRY(jh_blockop_bidiag_step(ops[0], us[0], t[0].p, t[0].s, -alpha, 1.0, &rr));
+                JH_TRY(pass[0].step(us[0], t[0].p, t[0].s, -alpha, 1.0, &rr));
             }
             double gamma_new = 0.0;
             JH_TRY(finish_s(&gamma_new));
@@ -1384,7 +1421,8 @@ extern "C" int jh_cgls_solve_team(int n, const jh_blockop *const *ops, jh_bvec *
 // Partitioned: every shard's A_k'A_k p in 4 element ranges (jh_blockop_normal_mul_range), each range all-reduced on the exchange stream
 // under the next range's kernel; the scalars come from the replicated vectors, so the exchange of y is the only collective.
 static int cgnr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *bs, jh_bvec *const *xs, int use_x0, double damp, double atol,
-                     double btol, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history, const Exch ex)
+                     double btol, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history, const Exch ex,
+                     const jh_chain *ch = nullptr)
 {
     JH_REQUIRE(ops && bs && xs && res && M >= 1, "jh_cgnr_solve: null argument");
     JH_REQUIRE(maxiter >= 0, "jh_cgnr_solve: maxiter must be >= 0");
@@ -1399,7 +1437,7 @@ static int cgnr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
         // (round 6: one shard may also be an N x (2 .. 4) grid of equal diagonals -- its fused A'A is jh_grid_normal.hip; the loop below only ever calls
         // jh_blockop_mul_adj and jh_blockop_normal_mul on whole vectors there)
         const bool grid = M == 1 && ex == Exch::none && jhb::grid_normal_ok(ops[k], xs[k]->data, xs[k]->data);
-        if (!grid && (!jh_blockop_tall_step_ok(ops[k], bs[k]->data, xs[k]->data) || ops[k]->nrow < 2))
+        if (!ch && !grid && (!jh_blockop_tall_step_ok(ops[k], bs[k]->data, xs[k]->data) || ops[k]->nrow < 2))
             return jh_fail(JH_ERR_UNSUPPORTED, "jh_cgnr_solve: needs a tall (>= 2 rows) operator of equal elementwise rows (or, unpartitioned, an N x (2 .. 4) grid of equal diagonals)");
     }
     struct Work {
@@ -1411,6 +1449,8 @@ static int cgnr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
             if (y) (void)jh_bvec_destroy(y);
         }
     };
+    std::vector<Passes> pass((size_t)M);
+    for (int k = 0; k < M; k++) { pass[k].op = ops[k]; pass[k].ch = ch; }
     std::vector<Work> t((size_t)M);
     const int64_t len1[1] = {n};
     for (int k = 0; k < M; k++) {
@@ -1452,11 +1492,11 @@ static int cgnr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
     }
     JH_TRY(global_sum(locals, &s2));
     const double bnorm = std::sqrt(s2);
-    for (int k = 0; k < M; k++) JH_TRY(jh_blockop_mul_adj(ops[k], t[k].s, bs[k]));
+    for (int k = 0; k < M; k++) JH_TRY(pass[k].adjoint(t[k].s, bs[k]));
     JH_TRY(allreduce([&](int k) { return t[k].s; }));
     double rr = s2;                                                       // ||b - A x||^2, by recurrence
     if (use_x0) {                                                         // s = A'b - (A'A + damp^2) x0 ;  ||r0||^2 = ||b||^2 - 2 Re<x0, A'b> + <x0, A'A x0>
-        for (int k = 0; k < M; k++) JH_TRY(jh_blockop_normal_mul(ops[k], t[k].y, xs[k]));
+        for (int k = 0; k < M; k++) JH_TRY(pass[k].normal(t[k].y, xs[k]));
         JH_TRY(allreduce([&](int k) { return t[k].y; }));
         double xb = 0.0, xax = 0.0, im = 0.0;
         JH_TRY(jh_dot(xs[0], t[0].s, &xb, &im));
@@ -1483,7 +1523,7 @@ static int cgnr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
     // y = sum over the shards of A_k'A_k p.  Partitioned: in 4 element ranges -- the all-reduce of a finished range runs on the exchange
     // stream while the kernel of the next range computes; the library streams then wait for the exchange (no host synchronisation)
     auto normal_all = [&]() -> int {
-        if (ex == Exch::none) return jh_blockop_normal_mul(ops[0], t[0].y, t[0].p);
+        if (ex == Exch::none) return pass[0].normal(t[0].y, t[0].p);
         for (int64_t lo = 0; lo < n; lo += chunk) {
             const int64_t cnt = lo + chunk < n ? chunk : n - lo;
             for (int k = 0; k < M; k++) JH_TRY(jh_blockop_normal_mul_range(ops[k], t[k].y, t[k].p, lo, cnt));
@@ -1584,4 +1624,39 @@ extern "C" int jh_cgnr_solve_team(int n, const jh_blockop *const *ops, jh_bvec *
                    "(jh_comm_init_all); found %s, rank %d of %d", k, k, n, has_comm == 2 ? "a team" : "no team", rank, nranks);
     }
     return cgnr_impl(n, ops, bs, xs, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history, Exch::team);
+}
+
+// ------------------------------------------------------------------ the solvers on a FORWARD chain (weighted least squares) ---------------
+// lsqr(W o A o M, b) and its siblings (docs/src/index.md:235-246): the loops above with the four passes of the chain (Passes), one GPU, host-driven
+// at every size.  Declined (JH_ERR_UNSUPPORTED) before anything is touched where the step is: the caller keeps its generic loop.
+static int chain_solver_args(const jh_chain *fwd, const jh_bvec *u, const jh_bvec *x, const jh_blockop **op, const char *fn)
+{
+    JH_REQUIRE(fwd && u && x, "%s: null argument", fn);
+    JH_TRY(jhb::chain_solver_ok(fwd, u, x, op));
+    JH_TRY(jh_enter(*op, u, x));
+    return JH_OK;
+}
+
+extern "C" int jh_lsqr_solve_chain(const jh_chain *fwd, jh_bvec *u, jh_bvec *x, int use_x0, double damp, double atol, double btol, double conlim,
+                                   int maxiter, int force_maxiter, jh_lsqr_result *res, double *history)
+{
+    const jh_blockop *op = nullptr;
+    JH_TRY(chain_solver_args(fwd, u, x, &op, "jh_lsqr_solve_chain"));
+    return lsqr_impl(1, &op, &u, &x, use_x0, damp, atol, btol, conlim, maxiter, force_maxiter, res, history, Exch::none, fwd);
+}
+
+extern "C" int jh_cgls_solve_chain(const jh_chain *fwd, jh_bvec *u, jh_bvec *x, int use_x0, double damp, double atol, double btol, int maxiter,
+                                   int force_maxiter, jh_lsqr_result *res, double *history)
+{
+    const jh_blockop *op = nullptr;
+    JH_TRY(chain_solver_args(fwd, u, x, &op, "jh_cgls_solve_chain"));
+    return cgls_impl(1, &op, &u, &x, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history, Exch::none, fwd);
+}
+
+extern "C" int jh_cgnr_solve_chain(const jh_chain *fwd, jh_bvec *b, jh_bvec *x, int use_x0, double damp, double atol, double btol, int maxiter,
+                                   int force_maxiter, jh_lsqr_result *res, double *history)
+{
+    const jh_blockop *op = nullptr;
+    JH_TRY(chain_solver_args(fwd, b, x, &op, "jh_cgnr_solve_chain"));
+    return cgnr_impl(1, &op, &b, &x, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history, Exch::none, fwd);
 }

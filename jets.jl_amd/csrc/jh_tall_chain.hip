@@ -5,8 +5,10 @@
 
 namespace jhb {
 // the domain's elements [first_elem, end_elem) (not scalars: a complex element counts once)
-int chain_launch_adjoint(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem);   // jh_tall_chain_adj.hip
-int chain_launch_normal(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem);    // jh_tall_chain_nrm.hip
+// (ca: another program over the handle's rows and streams -- a FORWARD chain's derived ADJOINT / NORMAL program; NULL: the handle's own)
+int chain_launch_adjoint(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem, const ChainArgs *ca = nullptr);   // jh_tall_chain_adj.hip
+int chain_launch_normal(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem, const ChainArgs *ca = nullptr);    // jh_tall_chain_nrm.hip
+int chain_launch_step(const jh_chain *ch, const ChainArgs &ca, void *u, const void *v, void *w, double alpha, double beta, double *normsq);   // jh_tall_chain_step.hip
 }  // namespace jhb
 
 namespace {
@@ -50,6 +52,49 @@ int build_prog(const char *side, int n, const jh_chain_stage *st, int dtype, int
         }
     }
     return JH_OK;
+}
+
+// the adjoint of a stage list: the stages in reverse order, each its own adjoint -- a real scalar is itself (conj(a) == a, src/Jets.jl:1160), a
+// diagonal its conjugate (the same array and stream; a row's own conj flag and a block operator's ROWSUM stay: the kernel flips per row).  `at`:
+// where in `out` they go.  Returns the number of stages.
+int adjoint_prog(const ChainProg &in, ChainProg &out, int at)
+{
+    int n = 0;
+    while (n < JH_CHAIN_MAX_STAGES && (in.st[n] & 15u) != CK_NONE) n++;
+    for (int s = 0; s < n && at + s < JH_CHAIN_MAX_STAGES; s++) {
+        const int from = n - 1 - s;
+        uint32_t w = in.st[from];
+        const uint32_t k = w & 15u;
+        if (k == CK_DIAG || k == CK_DIAG_CONJ) w = (w & ~15u) | (k == CK_DIAG ? CK_DIAG_CONJ : CK_DIAG);
+        out.st[at + s] = w;
+        out.a32[at + s] = in.a32[from];
+        out.a[at + s] = in.a[from];
+    }
+    return n;
+}
+
+// the ADJOINT, NORMAL and step programs of a FORWARD chain (jh_chain::adj_args, nrm_args, step_args)
+void derive_progs(jh_chain *ch)
+{
+    const ChainArgs &f = ch->args;
+    ChainArgs adj{}, nrm{};
+    for (int s = 0; s < JH_CHAIN_MAX_STAGES; s++) adj.pre.st[s] = adj.mid.st[s] = adj.post.st[s] = nrm.mid.st[s] = nrm.post.st[s] = CK_NONE;
+    adj.rows = nrm.rows = f.rows;
+    (void)adjoint_prog(f.mid, adj.mid, 0);
+    (void)adjoint_prog(f.pre, adj.post, 0);
+    for (int q = 0; q < JH_CHAIN_MAX_STREAMS; q++) adj.post_c[q] = nrm.post_c[q] = nrm.pre_c[q] = f.pre_c[q];
+    nrm.pre = f.pre;
+    nrm.mid = f.mid;
+    nrm.post = adj.post;
+    int nr = 0;
+    while (nr < JH_CHAIN_MAX_STAGES && (f.mid.st[nr] & 15u) != CK_NONE) nr++;
+    ch->nrm_ok = 2 * nr <= JH_CHAIN_MAX_STAGES;
+    if (ch->nrm_ok) (void)adjoint_prog(f.mid, nrm.mid, nr);
+    ChainArgs stp = nrm;                     // the step: R alone in the range-side list (k_chain_adj MODE 2 applies R^H from it, mid_step)
+    stp.mid = f.mid;
+    ch->step_args = stp;
+    ch->adj_args = adj;
+    ch->nrm_args = nrm;
 }
 
 // word 0 of every record from the operator's blocks as they are NOW, then the table to the device (at create, and again when jh_blockop_point has
@@ -146,6 +191,7 @@ int jh_chain_create(const jh_blockop *op, int type, int npre, const jh_chain_sta
         if (st2 != JH_OK) { (void)hipFree(ch->dev_tab); delete ch; return st2; }
     }
     ch->stream_bytes = (double)op->nrow * (double)op->row_len[0] * (double)es * (double)(1 + ch->nw);
+    if (type == JH_CHAIN_FORWARD) derive_progs(ch);
     jh_handle_born(ch->ctx);
     *out = ch;
     return JH_OK;
@@ -210,7 +256,82 @@ int jh_chain_apply_range(const jh_chain *ch, jh_bvec *out, const jh_bvec *x, int
     return jhb::chain_launch_normal(ch, out->data, x->data, accumulate, first_elem, first_elem + count);
 }
 
+// the checks of the step and of the derived applications of a FORWARD chain: handle type, the operator's point, the row table (refreshed when the operator
+// was pointed again -- declined while the stream is capturing: the copy to the device would be captured)
+static int fwd_ready(const jh_chain *ch, const char *fn)
+{
+    JH_REQUIRE(ch->type == JH_CHAIN_FORWARD, "%s: needs a FORWARD chain (got type %d)", fn, ch->type);
+    const jh_blockop *op = ch->op;
+    if (op->nonlinear && !op->pointed)
+        return jh_fail(JH_ERR_STATE, "%s: operator has nonlinear blocks and no linearisation point (jh_blockop_point)", fn);
+    if (ch->op_gen != op->table_gen) {
+        if (jhb::stream_is_capturing(jh_ctx().stream))
+            return jh_fail(JH_ERR_UNSUPPORTED, "%s: the operator was pointed again since the chain's row table was built, and the stream is capturing", fn);
+        JH_TRY(chain_sync_rows(const_cast<jh_chain *>(ch)));
+    }
+    return JH_OK;
+}
+
+// u <- alpha L v + beta u ;  w = L'u ;  ||u||^2 for L = R o A o P, in ONE pass (k_chain_adj MODE 2)
+int jh_chain_bidiag_step(const jh_chain *fwd, jh_bvec *u, const jh_bvec *v, jh_bvec *w, double alpha, double beta, double *normsq)
+{
+    JH_REQUIRE(fwd && u && v && w, "jh_chain_bidiag_step: null argument");
+    JH_REQUIRE(fwd->type == JH_CHAIN_FORWARD, "jh_chain_bidiag_step: needs a FORWARD chain (got type %d)", fwd->type);
+    if (!fwd->nrm_ok)
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step: R and R^H need more than %d range-side stages", JH_CHAIN_MAX_STAGES);
+    const jh_blockop *op = fwd->op;
+    JH_TRY(jh_enter(op, u, v, w));
+    const int64_t nrange = op->row_off[(size_t)op->nrow], ndom = op->col_off[(size_t)op->ncol];
+    JH_REQUIRE(u->dtype == op->dtype && v->dtype == op->dtype && w->dtype == op->dtype, "jh_chain_bidiag_step: dtype mismatch");
+    JH_REQUIRE(u->length == nrange && v->length == ndom && w->length == ndom, "jh_chain_bidiag_step: u must be a range vector, v and w domain vectors of the operator");
+    JH_REQUIRE(w->data != v->data && u->data != v->data && u->data != w->data, "jh_chain_bidiag_step: u, v and w must be three vectors");
+    if (!jhb::tall_unaligned_ok(op, u->data, v->data) || !jhb::tall_unaligned_ok(op, nullptr, w->data))
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step: a vector or coefficient array is not aligned like its scalar");
+    JH_TRY(fwd_ready(fwd, "jh_chain_bidiag_step"));
+    return jhb::chain_launch_step(fwd, fwd->step_args, u->data, v->data, w->data, alpha, beta, normsq);
+}
+
 }  // extern "C"
+
+namespace jhb {
+// L' (which == JH_CHAIN_ADJOINT: out = L' in, in a range vector) or L'L (JH_CHAIN_NORMAL) of a FORWARD chain, through the derived programs: the solver
+// loops of jh_lsqr.hip on a chain
+int chain_apply_derived(const jh_chain *fwd, int which, jh_bvec *out, const jh_bvec *in)
+{
+    JH_REQUIRE(fwd && out && in, "chain_apply_derived: null argument");
+    const jh_blockop *op = fwd->op;
+    JH_TRY(jh_enter(op, out, in));
+    JH_TRY(fwd_ready(fwd, "chain_apply_derived"));
+    if (which == JH_CHAIN_NORMAL && !fwd->nrm_ok)
+        return jh_fail(JH_ERR_UNSUPPORTED, "chain_apply_derived: R and R^H need more than %d range-side stages", JH_CHAIN_MAX_STAGES);
+    const int64_t nrange = op->row_off[(size_t)op->nrow], ndom = op->col_off[(size_t)op->ncol];
+    JH_REQUIRE(out->dtype == op->dtype && in->dtype == op->dtype && out->data != in->data, "chain_apply_derived: dtype mismatch or aliasing");
+    JH_REQUIRE(out->length == ndom && in->length == (which == JH_CHAIN_ADJOINT ? nrange : ndom), "chain_apply_derived: vector lengths");
+    const bool ok = which == JH_CHAIN_ADJOINT ? jhb::tall_unaligned_ok(op, in->data, out->data)
+                                              : jhb::tall_unaligned_ok(op, nullptr, out->data) && jhb::tall_unaligned_ok(op, nullptr, in->data);
+    if (!ok) return jh_fail(JH_ERR_UNSUPPORTED, "chain_apply_derived: a vector is not aligned like its scalar");
+    if (which == JH_CHAIN_ADJOINT) return chain_launch_adjoint(fwd, out->data, in->data, 0, 0, out->length, &fwd->adj_args);
+    return chain_launch_normal(fwd, out->data, in->data, 0, 0, out->length, &fwd->nrm_args);
+}
+}  // namespace jhb
+
+namespace jhb {
+// may the solver loops run on this chain (jh_*_solve_chain)?  The checks of jh_chain_bidiag_step on the solver's vectors, before anything is touched
+int chain_solver_ok(const jh_chain *fwd, const jh_bvec *u, const jh_bvec *x, const jh_blockop **op)
+{
+    JH_REQUIRE(fwd->type == JH_CHAIN_FORWARD, "jh_*_solve_chain: needs a FORWARD chain (got type %d)", fwd->type);
+    if (!fwd->nrm_ok)
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_*_solve_chain: R and R^H need more than %d range-side stages", JH_CHAIN_MAX_STAGES);
+    const jh_blockop *o = fwd->op;
+    const int64_t nrange = o->row_off[(size_t)o->nrow], ndom = o->col_off[(size_t)o->ncol];
+    JH_REQUIRE(u->dtype == o->dtype && x->dtype == o->dtype && u->length == nrange && x->length == ndom,
+               "jh_*_solve_chain: the right-hand side must be a range vector and x a domain vector of the chain's operator");
+    if (!tall_unaligned_ok(o, u->data, x->data))
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_*_solve_chain: a vector is not aligned like its scalar");
+    *op = o;
+    return JH_OK;
+}
+}  // namespace jhb
 
 // ---- the chain kernels as the library's own adjoint / fused A'A of operators with rows of several kinds (round 6) -----------------------------------
 // With EMPTY stage lists the ADJOINT chain is m = sum_i conj(a_i) .* d_i -- jh_blockop_mul_adj --, the NORMAL chain jh_blockop_normal_mul, over packed 8-byte row records requested a batch ahead,

@@ -33,6 +33,9 @@ constexpr int JH_CHAIN_MAX_STREAMS = 2;  // DIAG stages per side that read a coe
 enum { CK_NONE = 0, CK_SCALE = 1, CK_SCALE_WIDE = 2, CK_DIAG = 3, CK_DIAG_CONJ = 4 };
 enum : uint32_t { CK_ROWSUM = 1u << 8 };        // (stage word: kind | stream << 4 | CK_ROWSUM)
 
+}  // namespace
+
+// (the program structs have linkage: the launchers of the other translation units take them by reference)
 // One side's stage list, packed for the scalar unit: a stage is ONE 32-bit word (kind | stream << 4) and its scalar one float (32-bit elements) or
 // double -- the range-side list lives in SGPRs for the whole row loop, beside the rows' table entries and the streams' base addresses.
 struct ChainProg {
@@ -42,6 +45,15 @@ struct ChainProg {
                                          //  through a 20-byte stack copy of the argument -- a scratch frame nobody reads, but a scratch frame)
     double a[JH_CHAIN_MAX_STAGES];       // SCALE on 64-bit elements; WIDE: Julia's Float64 scalar against 32-bit elements
 };
+
+struct ChainArgs {
+    ChainProg pre, mid, post;
+    const void *pre_c[JH_CHAIN_MAX_STREAMS];       // domain-sized coefficient arrays of P
+    const void *post_c[JH_CHAIN_MAX_STREAMS];      // ... of Q
+    const uint64_t *rows;                          // the row table: nrow records of (1 + NW) words
+};
+
+namespace {
 
 // THE ROW TABLE.  One record of (1 + NW) 64-bit words per block row, built when the chain is created: word 0 describes A's block of the row, words
 // 1 .. NW the row's blocks of the range-side coefficient streams.  A word is a device pointer (48 bits) with its flags above it -- one s_load_dwordx2 per
@@ -59,13 +71,6 @@ __device__ inline bool cr_reads(uint64_t e) { const int k = cr_kind(e); return k
 __device__ inline bool cw_conj(uint64_t e) { return ((e >> 48) & 1u) != 0; }
 __device__ inline bool cw_zero(uint64_t e) { return ((e >> 49) & 1u) != 0; }
 template <typename S> __device__ inline const S *cr_ptr(uint64_t e) { return reinterpret_cast<const S *>(e & CR_PTR); }
-
-struct ChainArgs {
-    ChainProg pre, mid, post;
-    const void *pre_c[JH_CHAIN_MAX_STREAMS];       // domain-sized coefficient arrays of P
-    const void *post_c[JH_CHAIN_MAX_STREAMS];      // ... of Q
-    const uint64_t *rows;                          // the row table: nrow records of (1 + NW) words
-};
 
 // x .= a * x for a REAL scalar: part by part (Julia's a::Real * z, src/Jets.jl:1159); WIDE: the promoted product rounded once
 template <typename S, int NS, typename V> __device__ inline V stage_scale(const ChainProg &p, int s, bool wide, V x)
@@ -149,6 +154,23 @@ __device__ inline V mid_prog(const ChainProg &p, V t, const V *wv, const uint64_
     const uint32_t k3 = p.st[3] & 15u;
     if (k3 == CK_NONE) return t;
     return mid_stage<S, E, NS, NW, V>(p, 3, k3, t, wv, e);
+}
+
+// the Golub-Kahan step's range-side lists (MODE 2): R is the FORWARD chain's own list of at most two stages (R + R^H fit the four of a NORMAL list:
+// jh_chain_bidiag_step declines longer ones), R^H the same stages in reverse order, each diagonal conjugated (a real scalar is its own adjoint).
+// HALF 0 applies R, HALF 1 R^H; both name the stages by constant index, so the list stays in SGPRs as in mid_prog.
+__device__ inline uint32_t adj_kind(uint32_t k) { return k == CK_DIAG ? CK_DIAG_CONJ : (k == CK_DIAG_CONJ ? CK_DIAG : k); }
+template <int HALF, typename S, int E, int NS, int NW, typename V>
+__device__ inline V mid_step(const ChainProg &p, V t, const V *wv, const uint64_t *e)
+{
+    const uint32_t k0 = p.st[0] & 15u, k1 = p.st[1] & 15u;
+    if (k0 == CK_NONE) return t;
+    if (HALF == 0) {
+        t = mid_stage<S, E, NS, NW, V>(p, 0, k0, t, wv, e);
+        return k1 == CK_NONE ? t : mid_stage<S, E, NS, NW, V>(p, 1, k1, t, wv, e);
+    }
+    if (k1 != CK_NONE) t = mid_stage<S, E, NS, NW, V>(p, 1, adj_kind(k1), t, wv, e);
+    return mid_stage<S, E, NS, NW, V>(p, 0, adj_kind(k0), t, wv, e);
 }
 
 template <typename S, int NS, typename V> __device__ inline V chain_accumulate(int accumulate, V found, V r)
@@ -241,12 +263,16 @@ __global__ __launch_bounds__(BLK) void k_chain_fwd(const jh_dev_block *__restric
 
 // ------------------------------------------------------------------ ADJOINT / NORMAL -----------------------------------------------------
 // MODE 0:  out = Q( sum_i conj(a_i) .* R(d_i) )          MODE 1:  out = Q( sum_i conj(a_i) .* R(a_i .* P(in)) )
+// MODE 2 (the Golub-Kahan step of a FORWARD chain, jh_chain_bidiag_step): MODE 1 with R^H after R (mid_step) and the update of u between them --
+//   t_i = R(a_i .* P(in)) ;  u_i <- alpha t_i + beta u_i (beta == 0: u not read) ;  out = Q( sum_i conj(a_i) .* R^H(u_i) ) ;  partial ||u||^2
+// u_i is written by the lane that owns the pack (st_pack), so the rows' updates need no other lane; ||u||^2 is one fp64 partial per workgroup.
 // The ordered walk of k_tall_diag_adj (jh_tall.hip): a thread owns U packs of the domain and walks all rows in order, DEPTH rows' loads in flight, the
 // next DEPTH rows' table records already requested.
 template <typename S, int E, int NS, int U, int DEPTH, bool NT, int MODE, int BLK, int NW>
 __global__ __launch_bounds__(BLK) void k_chain_adj(const jh_dev_block *__restrict__ blocks, int64_t nrow, const ChainArgs ca, S *__restrict__ out,
                                                    const S *__restrict__ in, int64_t n_scalars, int64_t s_begin, int64_t s_end, int accumulate,
-                                                   int64_t rows_per_part, S *__restrict__ part_out)
+                                                   int64_t rows_per_part, S *__restrict__ part_out, S *__restrict__ u, S alpha, S beta,
+                                                   double *__restrict__ partials)
 {
     // n_scalars: a row's length (the range vector's row stride); the launch covers the domain's scalars [s_begin, s_end) -- the whole vector, or one
     // range of jh_chain_apply_range when the exchange is pipelined range by range (the bounds of k_tall_diag_adj, jh_tall.hip)
@@ -261,11 +287,24 @@ __global__ __launch_bounds__(BLK) void k_chain_adj(const jh_dev_block *__restric
         ok[k] = (s0 + (int64_t)k * BLK * NS) < s_end;
         sk[k] = pack_start<NS>(ok[k] ? s0 + (int64_t)k * BLK * NS : s_begin, s_end);   // (a range shorter than one pack ends with the vector: loaded from s_end - NS)
         acc[k] = (V)(S)0;                                                               // m .= 0 (1042)
-        if (MODE == 1) mv[k] = ldu<false, S, NS>(in + sk[k]);
+        if (MODE >= 1) mv[k] = ldu<false, S, NS>(in + sk[k]);
     }
+    const bool old_u = MODE == 2 && beta != (S)0;                                       // (beta == 0: u is write-only)
+    double nrm = 0.0;
+    // MODE 2: u_i <- alpha t + beta u_i, stored and counted from the first scalar the lane owns (a row's partial last pack, jh_blockop_common.h), then R^H
+    auto update = [&](int64_t row, int k, V t, V uo) -> V {
+        V r = (V)alpha * t;
+        if (old_u) { const V s2 = (V)beta * uo; r = r + s2; }
+        if (ok[k]) {
+            const int64_t sown = s0 + (int64_t)k * BLK * NS;
+            st_pack<NT, S, NS>(u + row * n_scalars, sown, sk[k], r);
+            nrm += vnorm2_from<S, NS, V>(r, (int)(sown - sk[k]));
+        }
+        return r;
+    };
     // (behind ONE wave-uniform test of the list's first stage, and after the loads: spelled inside the loop above, the stage list left 28 instantiations
     // with a 68-byte scratch frame that no instruction touches -- tools/kernel_resources.py)
-    if (MODE == 1 && (ca.pre.st[0] & 15u) != CK_NONE) {
+    if (MODE >= 1 && (ca.pre.st[0] & 15u) != CK_NONE) {
 #pragma unroll
         for (int k = 0; k < U; k++) mv[k] = dom_prog<S, E, NS, V>(ca.pre, ca.pre_c[0], ca.pre_c[1], mv[k], sk[k]);
     }
@@ -293,6 +332,7 @@ __global__ __launch_bounds__(BLK) void k_chain_adj(const jh_dev_block *__restric
                     for (int k = 0; k < U; k++) {
                         av[j][k] = ldu<NT, S, NS>(cr_ptr<S>(e[j][0]) + sk[k]);
                         if (MODE == 0) dv[j][k] = ldu<NT, S, NS>(in + (i + j) * n_scalars + sk[k]);
+                        if (MODE == 2) dv[j][k] = old_u ? ldu<NT, S, NS>(u + (i + j) * n_scalars + sk[k]) : (V)(S)0;
 #pragma unroll
                         for (int w = 0; w < NW; w++) wv[j][k][w] = ldu<NT, S, NS>(cr_ptr<S>(e[j][1 + w]) + sk[k]);
                     }
@@ -301,6 +341,12 @@ __global__ __launch_bounds__(BLK) void k_chain_adj(const jh_dev_block *__restric
 #pragma unroll
                     for (int k = 0; k < U; k++) {
                         V t = (MODE == 0) ? dv[j][k] : vmul<S, E, NS, V>(av[j][k], mv[k], false);
+                        if constexpr (MODE == 2) {
+                            t = mid_step<0, S, E, NS, NW, V>(ca.mid, t, wv[j][k], e[j]);
+                            t = mid_step<1, S, E, NS, NW, V>(ca.mid, update(i + j, k, t, dv[j][k]), wv[j][k], e[j]);
+                            acc[k] = acc[k] + vmul<S, E, NS, V>(av[j][k], t, true);
+                            continue;
+                        }
                         if (NW > 0 || (ca.mid.st[0] & 15u) != CK_NONE) t = mid_prog<S, E, NS, NW, V>(ca.mid, t, wv[j][k], e[j]);
                         acc[k] = acc[k] + vmul<S, E, NS, V>(av[j][k], t, true);
                     }
@@ -309,17 +355,33 @@ __global__ __launch_bounds__(BLK) void k_chain_adj(const jh_dev_block *__restric
         }
 #pragma unroll
         for (int j = 0; j < D; j++) {
-            const bool on = cr_kind(e[j][0]) != JH_OP_ZERO, rc = cr_reads(e[j][0]);
+            // (MODE 2: a zero block of A still has its row of u updated -- the FORWARD chain's zeros through R, then alpha t + beta u -- so the row's
+            //  weights and u are loaded all the same; it adds nothing to the sum, 1047)
+            const bool on = cr_kind(e[j][0]) != JH_OP_ZERO, rc = cr_reads(e[j][0]), onw = MODE == 2 || on;
 #pragma unroll
             for (int k = 0; k < U; k++) {
                 av[j][k] = rc ? ldu<NT, S, NS>(cr_ptr<S>(e[j][0]) + sk[k]) : (V)(S)0;
                 dv[j][k] = (MODE == 0 && on) ? ldu<NT, S, NS>(in + (i + j) * n_scalars + sk[k]) : (V)(S)0;
+                if (MODE == 2) dv[j][k] = old_u ? ldu<NT, S, NS>(u + (i + j) * n_scalars + sk[k]) : (V)(S)0;
 #pragma unroll
                 for (int w = 0; w < NWA; w++) {
                     const uint64_t we = e[j][NW > 0 ? 1 + w : 0];
-                    wv[j][k][w] = (NW > 0 && on && (we & CR_PTR)) ? ldu<NT, S, NS>(cr_ptr<S>(we) + sk[k]) : (V)(S)0;
+                    wv[j][k][w] = (NW > 0 && onw && (we & CR_PTR)) ? ldu<NT, S, NS>(cr_ptr<S>(we) + sk[k]) : (V)(S)0;
                 }
             }
+        }
+        if constexpr (MODE == 2) {
+#pragma unroll
+            for (int j = 0; j < D; j++) {
+                const bool on = cr_kind(e[j][0]) != JH_OP_ZERO;
+#pragma unroll
+                for (int k = 0; k < U; k++) {
+                    V t = on ? chain_apply_row<S, E, NS, V>(e[j][0], blocks, i + j, mv[k], av[j][k], false) : (V)(S)0;   // the FORWARD chain's row (1022)
+                    t = update(i + j, k, mid_step<0, S, E, NS, NW, V>(ca.mid, t, wv[j][k], e[j]), dv[j][k]);
+                    if (on) acc[k] = acc[k] + chain_apply_row<S, E, NS, V>(e[j][0], blocks, i + j, mid_step<1, S, E, NS, NW, V>(ca.mid, t, wv[j][k], e[j]), av[j][k], true);
+                }
+            }
+            return;
         }
 #pragma unroll
         for (int j = 0; j < D; j++)
@@ -366,6 +428,7 @@ __global__ __launch_bounds__(BLK) void k_chain_adj(const jh_dev_block *__restric
         for (int w = 0; w < RW; w++) e.w[0][w] = ca.rows[i * RW + w];
         batch(i, e, std::integral_constant<int, 1>{});
     }
+    if constexpr (MODE == 2) wg_sum_store<BLK>(nrm, partials + (int64_t)blockIdx.y * gridDim.x + blockIdx.x);   // by (part, tile): a fixed fold order
     if (part_out) {
         S *slab = part_out + (int64_t)blockIdx.y * (s_end - s_begin) - s_begin;
 #pragma unroll
@@ -411,6 +474,11 @@ struct jh_chain {
     int64_t op_gen = -1;                     //  the SQUARE rows' arrays) and the operator's table generation it was built for
     bool coeff16 = true;                     // every coefficient array of the stages on the 16-byte grid
     double stream_bytes = 0;                 // N n s (1 + nw): what one pass streams besides the vectors
+    // a FORWARD chain L = R o A o P also carries the programs of L' (ADJOINT: mid R^H, post Q = P^H), of L'L (NORMAL: pre P, mid [R..., R^H...],
+    // post Q) and of its Golub-Kahan step (pre P, mid R, post Q; MODE 2 applies R^H from R): built from the handle's own lists at create, over the same
+    // row table and streams
+    ChainArgs adj_args{}, nrm_args{}, step_args{};
+    bool nrm_ok = false;                     // R + R^H fit one list (<= JH_CHAIN_MAX_STAGES stages)
 };
 
 namespace {
@@ -450,17 +518,27 @@ int launch_chain_fwd(const jh_chain *ch, void *d, const void *m, int64_t n_scala
 // call and a range both walk the rows in one part they have the same bits (every scalar is its own ordered row sum); where the part counts differ
 // (many rows of small blocks: pick_adj_parts) the fold adds different partial sums -- tolerance parity, DESIGN.md section 3.  The nontemporal choice
 // stays the whole application's: a range's coefficients come back one application later, after every other range's.
+// The step's extra operands (MODE 2): u, its coefficients and where ||u||^2 goes (NULL: not read back)
+struct ChainStep {
+    void *u = nullptr;
+    double alpha = 1.0, beta = 0.0;
+    double *normsq = nullptr;
+};
+
+// `ca`: the handle's own program, or one derived from it (the ADJOINT / NORMAL / step programs of a FORWARD chain: jh_tall_chain.hip)
 template <typename S, int E, int NS, int MODE>
-int launch_chain_adj(const jh_chain *ch, void *out, const void *in, int64_t n_scalars, int accumulate, int64_t s_begin, int64_t s_end)
+int launch_chain_adj(const jh_chain *ch, const ChainArgs &ca, void *out, const void *in, int64_t n_scalars, int accumulate, int64_t s_begin, int64_t s_end,
+                     const ChainStep *step = nullptr)
 {
     jh_context &c = jh_ctx();
     const jh_blockop *op = ch->op;
     const int64_t span = s_end - s_begin;
     if (span <= 0) return JH_OK;
+    if (MODE == 2 && !step) return jh_fail(JH_ERR_INVALID, "chain step: no step operands");
     const int64_t packs = (span + NS - 1) / NS;
     const int64_t row_bytes = n_scalars * (int64_t)sizeof(S);
     const bool off_grid = row_bytes % 16 != 0 || !op->coeff_aligned16 || !ch->coeff16 || ((((uintptr_t)out) | ((uintptr_t)in)) & 15u) != 0;
-    const double streamed = ch->stream_bytes + (MODE == 0 ? (double)op->nrow * (double)row_bytes : 0.0);
+    const double streamed = ch->stream_bytes + (MODE != 1 ? (double)op->nrow * (double)row_bytes : 0.0);   // (MODE 2: u, read and written)
     const bool nt = jh_stream_nt(streamed) && !(c.ua_nt == 0 || (c.ua_nt < 0 && off_grid && row_bytes >= ((int64_t)32 << 20)));
     // shapes (lanes x packs per lane x rows in flight): thin workgroups (256 x 1 x 4) for rows of a few KiB, 512 x 2 x 2 in between, fat ones (512 x 4 x 2) once
     // a row holds >= 256 K packs (4 MiB of Float32: the all-diagonal adjoint's rule, jh_tall.hip: pick_adj_shape); the streams in flight per row are
@@ -470,6 +548,8 @@ int launch_chain_adj(const jh_chain *ch, void *out, const void *in, int64_t n_sc
     int shape = packs < 2048 ? 0 : (packs >= ((int64_t)1 << 18) ? 2 : 1);
     while (shape > 0 && (packs + per_wg_of[shape] - 1) / per_wg_of[shape] < c.cu_count) shape--;   // a workgroup per CU at least, if the rows are long enough for it
     if (c.adj_wg == 256) shape = 0; else if (c.adj_wg == 512 && c.adj_unroll == 4) shape = 2; else if (c.adj_wg == 512) shape = 1;
+    // the step of ComplexF32 has no fat shape (512 x 4 x 1 spills SGPRs past the family's census): capped HERE, before the grid is sized from the shape
+    if (MODE == 2 && E == 2 && sizeof(S) == 4 && shape == 2) shape = 1;
     const int64_t per_wg = per_wg_of[shape];
     const int64_t gx = (packs + per_wg - 1) / per_wg;
     // many rows of small blocks: the split-row walk (jh_tall.hip: pick_adj_parts; adj_split = 0 keeps the ordered, bit-exact walk) -- parts of the row sum into
@@ -479,7 +559,7 @@ int launch_chain_adj(const jh_chain *ch, void *out, const void *in, int64_t n_sc
     // (one workgroup per CU, up to two: the chain's three or four streams per row leave the ordered walk latency-bound there -- 4096 x 64^3, 256 workgroups:
     // A' o W o A 4.37 TB/s in one part, 7.04 in two, 6.3 in four or more; profiles/bench_chains_r06_split.txt)
     if (parts == 1 && c.adj_split < 0 && span >= NS && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
-    const bool finish = accumulate != 0 || (ch->args.post.st[0] & 15u) != CK_NONE;
+    const bool finish = accumulate != 0 || (ca.post.st[0] & 15u) != CK_NONE;
     S *slabs = nullptr, *folded = (S *)out;
     if (parts > 1) {
         rows_per_part = (op->nrow + parts - 1) / parts;
@@ -490,9 +570,17 @@ int launch_chain_adj(const jh_chain *ch, void *out, const void *in, int64_t n_sc
         if (finish) folded = slabs + parts * span - s_begin;                                    // (addressed like `out`: scalar s at folded + s)
     }
     c.last_adj_parts = parts;
+    S *u = nullptr, alpha = (S)0, beta = (S)0;
+    if (MODE == 2) {
+        JH_TRY(jh_ensure_partials(gx * parts));
+        u = (S *)step->u;
+        alpha = (S)step->alpha;
+        beta = (S)step->beta;
+    }
+    double *partials = MODE == 2 ? c.part_dev : nullptr;
 #define JH_CHAIN_ADJ(BLKV, UV, DV, NTV, NWV)                                                                                                 \
     hipLaunchKernelGGL((k_chain_adj<S, E, NS, UV, DV, NTV, MODE, BLKV, NWV>), dim3((unsigned)gx, (unsigned)parts), dim3(BLKV), 0, c.stream, op->dev_blocks, \
-                       op->nrow, ch->args, (S *)out, (const S *)in, n_scalars, s_begin, s_end, accumulate, rows_per_part, slabs)
+                       op->nrow, ca, (S *)out, (const S *)in, n_scalars, s_begin, s_end, accumulate, rows_per_part, slabs, u, alpha, beta, partials)
 #define JH_CHAIN_ADJ_NW(BLKV, UV, DV, NTV)                                                                                                    \
     switch (ch->nw) {                                                                                                                      \
     case 0: JH_CHAIN_ADJ(BLKV, UV, DV, NTV, 0); break;                                                                                     \
@@ -502,9 +590,17 @@ int launch_chain_adj(const jh_chain *ch, void *out, const void *in, int64_t n_sc
 #define JH_CHAIN_ADJ_SHAPE(NTV)                                                                                                              \
     /* (rows of a few hundred KiB at most, one workgroup per CU or fewer: eight rows in flight instead of four bought nothing -- 4096 x 64^3 3.79 -> 3.73   \
        TB/s -- and their sixteen row records pushed the SGPR spills past what fits the lanes of the spill registers) */                             \
-    if (shape == 0) { JH_CHAIN_ADJ_NW(256, 1, 4, NTV) }                                                                                    \
-    else if (shape == 1) { JH_CHAIN_ADJ_NW(512, 2, 2, NTV) }                                                                               \
-    else { JH_CHAIN_ADJ_NW(512, 4, 2, NTV) }
+    if constexpr (MODE == 2) {                                                                                                             \
+        /* (the step holds u's packs and the update beside the adjoint's state: half the rows in flight keeps the SGPR spills of the family's   \
+           census and the fat shape out of scratch) */                                                                                     \
+        if (shape == 0) { JH_CHAIN_ADJ_NW(256, 1, 2, NTV) }                                                                                \
+        else if (shape == 1) { JH_CHAIN_ADJ_NW(512, 2, 1, NTV) }                                                                           \
+        else if constexpr (!(E == 2 && sizeof(S) == 4)) { JH_CHAIN_ADJ_NW(512, 4, 1, NTV) }   /* (ComplexF32: shape 2 was capped above) */ \
+    } else {                                                                                                                               \
+        if (shape == 0) { JH_CHAIN_ADJ_NW(256, 1, 4, NTV) }                                                                                \
+        else if (shape == 1) { JH_CHAIN_ADJ_NW(512, 2, 2, NTV) }                                                                           \
+        else { JH_CHAIN_ADJ_NW(512, 4, 2, NTV) }                                                                                           \
+    }
     if (nt) { JH_CHAIN_ADJ_SHAPE(true) } else { JH_CHAIN_ADJ_SHAPE(false) }
 #undef JH_CHAIN_ADJ_SHAPE
 #undef JH_CHAIN_ADJ_NW
@@ -513,10 +609,14 @@ int launch_chain_adj(const jh_chain *ch, void *out, const void *in, int64_t n_sc
     if (parts > 1) {
         JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, span, parts, folded, s_begin, s_end));
         if (finish) {
-            hipLaunchKernelGGL((k_chain_finish<S, E, NS>), dim3((unsigned)((packs + 255) / 256)), dim3(256), 0, c.stream, ch->args, (S *)out, (const S *)folded,
+            hipLaunchKernelGGL((k_chain_finish<S, E, NS>), dim3((unsigned)((packs + 255) / 256)), dim3(256), 0, c.stream, ca, (S *)out, (const S *)folded,
                                s_begin, s_end, accumulate);
             JH_CHECK_HIP(hipGetLastError());
         }
+    }
+    if (MODE == 2) {
+        c.last_step_parts = gx * parts;
+        return jhb::step_finish_normsq(gx * parts, step->normsq);
     }
     return JH_OK;
 }

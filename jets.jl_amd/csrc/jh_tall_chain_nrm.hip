@@ -3,15 +3,16 @@
 #include "jh_tall_chain_kernels.h"
 
 namespace jhb {
-int chain_launch_normal(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem)
+int chain_launch_normal(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem, const ChainArgs *ca)
 {
+    const ChainArgs &args = ca ? *ca : ch->args;
     const jh_blockop *op = ch->op;
     const int64_t n = op->row_len[0];
     switch (op->dtype) {
-    case JH_F32: return launch_chain_adj<float, 1, 4, 1>(ch, out, in, n, accumulate, first_elem, end_elem);
-    case JH_F64: return launch_chain_adj<double, 1, 2, 1>(ch, out, in, n, accumulate, first_elem, end_elem);
-    case JH_C32: return launch_chain_adj<float, 2, 4, 1>(ch, out, in, n * 2, accumulate, first_elem * 2, end_elem * 2);
-    case JH_C64: return launch_chain_adj<double, 2, 2, 1>(ch, out, in, n * 2, accumulate, first_elem * 2, end_elem * 2);
+    case JH_F32: return launch_chain_adj<float, 1, 4, 1>(ch, args, out, in, n, accumulate, first_elem, end_elem);
+    case JH_F64: return launch_chain_adj<double, 1, 2, 1>(ch, args, out, in, n, accumulate, first_elem, end_elem);
+    case JH_C32: return launch_chain_adj<float, 2, 4, 1>(ch, args, out, in, n * 2, accumulate, first_elem * 2, end_elem * 2);
+    case JH_C64: return launch_chain_adj<double, 2, 2, 1>(ch, args, out, in, n * 2, accumulate, first_elem * 2, end_elem * 2);
     }
     return jh_fail(JH_ERR_INVALID, "chain_launch_normal: unknown dtype %d", op->dtype);
 }

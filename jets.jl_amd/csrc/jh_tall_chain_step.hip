@@ -1,0 +1,23 @@
+// jh_tall_chain_step.hip -- the Golub-Kahan step of a FORWARD chain  u_i <- alpha R(a_i .* P(v)) + beta u_i ; w = Q(sum_i conj(a_i) .* R^H(u_i)) ; ||u||^2
+// (MODE 2 of k_chain_adj, jh_tall_chain_kernels.h), a translation unit of its own (build time: see jh_tall_chain.hip).
+#include "jh_tall_chain_kernels.h"
+
+namespace jhb {
+int chain_launch_step(const jh_chain *ch, const ChainArgs &ca, void *u, const void *v, void *w, double alpha, double beta, double *normsq)
+{
+    const jh_blockop *op = ch->op;
+    const int64_t n = op->row_len[0];
+    ChainStep st;
+    st.u = u;
+    st.alpha = alpha;
+    st.beta = beta;
+    st.normsq = normsq;
+    switch (op->dtype) {
+    case JH_F32: return launch_chain_adj<float, 1, 4, 2>(ch, ca, w, v, n, 0, 0, n, &st);
+    case JH_F64: return launch_chain_adj<double, 1, 2, 2>(ch, ca, w, v, n, 0, 0, n, &st);
+    case JH_C32: return launch_chain_adj<float, 2, 4, 2>(ch, ca, w, v, n * 2, 0, 0, n * 2, &st);
+    case JH_C64: return launch_chain_adj<double, 2, 2, 2>(ch, ca, w, v, n * 2, 0, 0, n * 2, &st);
+    }
+    return jh_fail(JH_ERR_INVALID, "chain_launch_step: unknown dtype %d", op->dtype);
+}
+}  // namespace jhb

@@ -1009,6 +1009,10 @@ int launch_bidiag(const jh_blockop *op, void *u, const void *v, void *w, int64_t
 
 }  // namespace
 
+namespace jhb {
+int step_finish_normsq(int64_t nparts, double *normsq) { return finish_normsq(nparts, normsq); }
+}  // namespace jhb
+
 // into how many row ranges the one-pass step over the whole domain cuts this operator (1: one plain launch -- what the graph-replayed
 // solver loops of jh_lsqr.hip need, because only the plain launch reads its coefficients from the device)
 int64_t jh_bidiag_step_parts(const jh_blockop *op)

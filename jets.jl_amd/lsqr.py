@@ -72,6 +72,19 @@ class _Engine:
         self._tmp_r = None
         self._tmp_d = None
         self.fused_step = os.environ.get("JETS_LSQR_FUSED_STEP", "1") != "0"   # one pass per iteration (jh_blockop_bidiag_step)
+        # a composite that is ONE fused FORWARD chain (W o A, W o A o M, a * (W o A)): its one-pass step, its native solves and cgnr_core's
+        # NORMAL-chain hook (chains.SolverChains; JETS_CHAIN_STEP=0: the chain into a range temporary, then the ADJOINT chain).  One GPU only:
+        # the row-partitioned and team engines keep their routes.
+        self.chains = None
+        self._tmp_q = None
+        if self.native is None and type(self) is _Engine:
+            from . import chains as _chn
+
+            sc = _chn.SolverChains(self.L)
+            if sc.fwd is not None:
+                self.chains = sc
+                if sc.normal_planned():                   # (the NORMAL handle itself is built when cgnr_core first calls the hook)
+                    self.normal = self._chain_normal
 
     # --- vector algebra
     def zeros_dom(self):
@@ -143,8 +156,28 @@ class _Engine:
 
     def step(self, u, v, alpha, beta):
         """u <- alpha*(A v) + beta*u ; w <- A'u.  Returns (||u||, w) or None."""
+        if self.chains is not None and self.chains.fwd is not None and self.fused_step:
+            if self._tmp_d is None:
+                self._tmp_d = zeros(_j.domain(self.A))
+            nrm2 = self.chains.step(u, v, self._tmp_d, alpha, beta)
+            if nrm2 is not None:
+                return math.sqrt(nrm2), self._tmp_d
         r = self._step_local(u, v, alpha, beta)
         return None if r is None else (math.sqrt(r[0]), r[1])
+
+    def _chain_normal(self, y, p) -> float:
+        """y = L'L p as ONE NORMAL chain (cgnr_core's hook); returns <p, y>.  Should the library decline the handle, A then A' through a range
+        temporary -- what cgnr_core does without the hook."""
+        h = self.chains.normal()
+        if h is None:
+            if self._tmp_q is None:
+                self._tmp_q = zeros(_j.range_(self.A))
+            qn = self.fwd(self._tmp_q, p, 1.0, 0.0)
+            self.adj(y, self._tmp_q, 1.0, 0.0)
+            return qn * qn
+        h.apply(y, p)
+        v = dot(p, y)
+        return float(getattr(v, "real", v))
 
     def adj(self, v, u, alpha, beta) -> float:
         """v <- alpha*(A' u) + beta*v ; returns ||v||."""
@@ -303,7 +336,8 @@ def _native_solve(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, fo
     from ._ffi import LsqrResultC
     from .rowpart import AbiComm
 
-    if os.environ.get("JETS_LSQR_NATIVE", "1") == "0" or eng.native is None or not eng.fused_step:
+    chn = _chain_of(eng)
+    if os.environ.get("JETS_LSQR_NATIVE", "1") == "0" or (eng.native is None and chn is None) or not eng.fused_step:
         return None
     shard = getattr(eng, "shard", None)
     if shard is not None and not (isinstance(shard.comm, AbiComm) or shard.comm.world == 1):
@@ -314,15 +348,32 @@ def _native_solve(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, fo
     hist = (C.c_double * builtins.max(2 * int(maxiter), 1))()
     try:
         # a rank-local operator is solved locally even while an AbiComm is alive; only a RowPartitionedOp is a collective solve
-        solve = lib.jh_lsqr_solve_partitioned if shard is not None else lib.jh_lsqr_solve
-        check(solve(eng.native.handle, u.handle, x.handle, 0 if x0 is None else 1, float(damp), float(atol), float(btol),
+        if chn is not None:                                     # one FORWARD chain: jh_lsqr_solve_chain iterates on its one-pass step
+            solve, h = lib.jh_lsqr_solve_chain, chn.fwd.handle
+        else:
+            solve, h = (lib.jh_lsqr_solve_partitioned if shard is not None else lib.jh_lsqr_solve), eng.native.handle
+        check(solve(h, u.handle, x.handle, 0 if x0 is None else 1, float(damp), float(atol), float(btol),
                     float(conlim), int(maxiter), 1 if force_maxiter else 0, C.byref(res), hist))
     except JetsHipError as e:
         if e.status != 4:                                       # JH_ERR_UNSUPPORTED is raised before anything is touched: generic path
             raise
         return None
+    _count_chain_solve(chn)
     history = [(k + 1, hist[2 * k], hist[2 * k + 1]) for k in builtins.range(res.itn)]
     return LsqrResult(x, res.istop, res.itn, res.r1norm, res.r2norm, res.anorm, res.acond, res.arnorm, res.xnorm, history)
+
+
+def _chain_of(eng):
+    """The one-GPU engine's FORWARD chain (chains.SolverChains) when the solve runs on it, else None."""
+    chn = getattr(eng, "chains", None)
+    return chn if chn is not None and chn.fwd is not None and eng.native is None and getattr(eng, "shard", None) is None else None
+
+
+def _count_chain_solve(chn):
+    if chn is not None:
+        from . import chains as _chn
+
+        _chn.STATS["chain_solve_calls"] += 1
 
 
 def _native_team_solve(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, force_maxiter):

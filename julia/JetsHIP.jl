@@ -1013,10 +1013,34 @@ end
 
 # one whole Golub-Kahan step in one pass: u <- alpha*(A v) + beta*u ; w <- A'u ; returns ||u||   (3/5 of the bytes of the two halves)
 function bidiag_step!(u::BlockArray{T,<:HipArray{T}}, w::HipArray{T}, A::JopLn, v::HipArray{T}, alpha::Real, beta::Real) where {T}
+    h = tall_native(A, T)
+    h == C_NULL && return bidiag_step!(u, w, _plan_chain(A, T), v, alpha, beta)
     nrm2 = Ref{Cdouble}()
     check(ccall((:jh_blockop_bidiag_step, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ref{Cdouble}),
-                tall_native(A, T), handle(u), handle(v), handle(w), alpha, beta, nrm2))
+                h, handle(u), handle(v), handle(w), alpha, beta, nrm2))
     sqrt(nrm2[])
+end
+# the same step over a FORWARD chain L = R ∘ A ∘ P (a weighted operator W ∘ A, W ∘ A ∘ M, a * (W ∘ A): the composite 530-540 in the solvers' loop
+# 1138-1154): u <- alpha*(L v) + beta*u ; w <- L'u ; ||u|| in ONE pass over A, the weights and u (jh_chain_bidiag_step)
+function bidiag_step!(u::BlockArray{T,<:HipArray{T}}, w::HipArray{T}, chain::Ptr{Cvoid}, v::HipArray{T}, alpha::Real, beta::Real) where {T}
+    chain == C_NULL && error("bidiag_step!: needs a tall block operator or a composite that is one fused FORWARD chain")
+    nrm2 = Ref{Cdouble}()
+    check(ccall((:jh_chain_bidiag_step, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ref{Cdouble}),
+                chain, handle(u), handle(v), handle(w), alpha, beta, nrm2))
+    sqrt(nrm2[])
+end
+
+# the FORWARD chain handle of a composite that plans to ONE fused run R ∘ A ∘ P (W ∘ A, W ∘ A ∘ M, a * (W ∘ A)), or C_NULL: what the solvers below take
+# in place of a tall block operator (jh_*_solve_chain)
+function _plan_chain(L::Jop, ::Type{T}) where {T}
+    (L isa JopLn && jet(L).df! === JetComposite_df!) || return C_NULL
+    ops = state(L).ops
+    st = Any[_chain_stage(JopLn(ops[i]), T) for i = length(ops):-1:1]   # application order (530-534)
+    steps = _chain_segments(st)
+    (length(steps) == 1 && steps[1][1] === :chain && steps[1][2] == Cint(0)) || return C_NULL
+    _, ctype, t, pre, mid, post, _, _ = steps[1]
+    _chain_sides_ok(t, pre, mid, post) || return C_NULL
+    _chain_handle(ctype, t, pre, mid, post, T)
 end
 
 # the whole LSQR loop behind the ABI; `partitioned=true` is the row-partitioned solve (A, b = this rank's block rows, a
@@ -1025,9 +1049,15 @@ end
 struct jh_lsqr_result; istop::Int32; itn::Int32; r1norm::Cdouble; r2norm::Cdouble; anorm::Cdouble; acond::Cdouble; arnorm::Cdouble; xnorm::Cdouble; end
 function hip_lsqr!(x::HipArray{T}, A::JopLn, b::BlockArray{T,<:HipArray{T}}; x0::Bool=false, damp=0.0, atol=1e-6, btol=1e-6, conlim=1e8, maxiter=100, partitioned::Bool=false) where {T}
     h = tall_native(A, T)
-    h == C_NULL && error("hip_lsqr!: needs a tall block operator of device-native children")
+    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T) : C_NULL        # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain
+    h == C_NULL && c == C_NULL && error("hip_lsqr!: needs a tall block operator of device-native children, or a composite that is one fused FORWARD chain")
     res = Ref{jh_lsqr_result}()
     hist = Vector{Cdouble}(undef, 2 * maxiter)
+    if c != C_NULL
+        check(ccall((:jh_lsqr_solve_chain, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Cint, Cint, Ref{jh_lsqr_result}, Ptr{Cdouble}),
+                    c, handle(b), handle(x), x0, damp, atol, btol, conlim, maxiter, 0, res, hist))
+        return x, res[], reshape(hist, 2, :)[:, 1:res[].itn]
+    end
     if partitioned
         check(ccall((:jh_lsqr_solve_partitioned, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Cint, Cint, Ref{jh_lsqr_result}, Ptr{Cdouble}),
                     h, handle(b), handle(x), x0, damp, atol, btol, conlim, maxiter, 0, res, hist))
@@ -1042,9 +1072,15 @@ end
 # overwritten (it becomes r = b - A x).  `partitioned=true`: the row-partitioned solve, a collective like hip_lsqr!'s
 function hip_cgls!(x::HipArray{T}, A::JopLn, b::BlockArray{T,<:HipArray{T}}; x0::Bool=false, damp=0.0, atol=1e-6, btol=1e-6, maxiter=100, partitioned::Bool=false) where {T}
     h = tall_native(A, T)
-    h == C_NULL && error("hip_cgls!: needs a tall block operator of device-native children")
+    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T) : C_NULL        # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain
+    h == C_NULL && c == C_NULL && error("hip_cgls!: needs a tall block operator of device-native children, or a composite that is one fused FORWARD chain")
     res = Ref{jh_lsqr_result}()
     hist = Vector{Cdouble}(undef, 2 * max(maxiter, 1))
+    if c != C_NULL
+        check(ccall((:jh_cgls_solve_chain, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Cint, Cint, Ref{jh_lsqr_result}, Ptr{Cdouble}),
+                    c, handle(b), handle(x), x0, damp, atol, btol, maxiter, 0, res, hist))
+        return x, res[], reshape(hist, 2, :)[:, 1:res[].itn]
+    end
     if partitioned
         check(ccall((:jh_cgls_solve_partitioned, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Cint, Cint, Ref{jh_lsqr_result}, Ptr{Cdouble}),
                     h, handle(b), handle(x), x0, damp, atol, btol, maxiter, 0, res, hist))
@@ -1057,9 +1093,15 @@ end
 # CG on the normal equations through the fused A'A (one pass over the coefficients per iteration; b is only read)
 function hip_cgnr!(x::HipArray{T}, A::JopLn, b::BlockArray{T,<:HipArray{T}}; x0::Bool=false, damp=0.0, atol=1e-6, btol=1e-6, maxiter=100, partitioned::Bool=false) where {T}
     h = tall_native(A, T)
-    h == C_NULL && error("hip_cgnr!: needs a tall block operator of device-native children")
+    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T) : C_NULL        # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain
+    h == C_NULL && c == C_NULL && error("hip_cgnr!: needs a tall block operator of device-native children, or a composite that is one fused FORWARD chain")
     res = Ref{jh_lsqr_result}()
     hist = Vector{Cdouble}(undef, 2 * max(maxiter, 1))
+    if c != C_NULL
+        check(ccall((:jh_cgnr_solve_chain, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Cint, Cint, Ref{jh_lsqr_result}, Ptr{Cdouble}),
+                    c, handle(b), handle(x), x0, damp, atol, btol, maxiter, 0, res, hist))
+        return x, res[], reshape(hist, 2, :)[:, 1:res[].itn]
+    end
     if partitioned
         check(ccall((:jh_cgnr_solve_partitioned, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Cint, Cint, Ref{jh_lsqr_result}, Ptr{Cdouble}),
                     h, handle(b), handle(x), x0, damp, atol, btol, maxiter, 0, res, hist))
