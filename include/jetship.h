@@ -366,8 +366,19 @@ int jh_blocksum_mul_adj_typed(int nterms, const jh_blockop *const *ops, const do
  * Many rows of small blocks (hundreds of rows whose ordered walk would leave the chip idle): the ADJOINT / NORMAL chains sum their rows in parts
  * like jh_blockop_mul_adj (deterministic, tolerance parity; the stages after A' and the accumulation run on the folded sum;
  * jh_tune_set("adj_split", 0) keeps the ordered, bit-exact walk; counter "last_adj_parts").
- * JH_ERR_UNSUPPORTED (take the stage-by-stage chain): operators that are not tall / elementwise / equal rows, one-row operators, arrays not
- * aligned like their scalar. */
+ * GRID CHAINS: `op` may also be an N x K grid (N >= 2, K = 2 .. 4) of equal blocks of >= 16 bytes, each a diagonal, an adjointed diagonal, a zero,
+ * an identity or a real or complex scalar block (knob "grid_chain" = 1, the default) -- a multi-parameter operator (N shots x K parameters):
+ *     FORWARD   out_i = R( ((0 + a_i1 .* P(x)_1) + a_i2 .* P(x)_2) + ... )        (JetBlock_df!, 1010-1032, a zero block skipped)
+ *     ADJOINT   out_k = Q( ((0 + conj(a_1k) .* R(x_1)) + conj(a_2k) .* R(x_2)) + ... )   (JetBlock_df'!, 1034-1057)
+ *     NORMAL    out_k = Q( sum_i conj(a_ik) .* R( sum_k' a_ik' .* P(x)_k' ) )
+ * with the same stage lists: P and Q on the whole domain vector (a DIAG coefficient array of K n elements), R per block row; the same bits as the
+ * stage-by-stage composite, every coefficient read once.  jh_chain_apply and jh_chain_destroy work unchanged, accumulate included; the many-small-
+ * rows split walk sums in parts as above.  jh_chain_apply_range and jh_chain_bidiag_step on a grid chain return JH_ERR_UNSUPPORTED before touching
+ * anything (no ranged form, no one-pass step), and so do jh_lsqr_solve_chain and jh_cgls_solve_chain on a grid FORWARD chain (keep the two-pass
+ * loops: two fused grid chains); jh_cgnr_solve_chain runs on the derived ADJOINT and NORMAL programs.  Counter "last_grid_chain_shape": bit 0
+ * nontemporal loads, bit 1 rows in parts, bit 2 the stages after A' run on the folded parts.  Knob "grid_chain" = 0: grids are declined as before.
+ * JH_ERR_UNSUPPORTED (take the stage-by-stage chain): operators that are not tall or such a grid / elementwise / equal rows, one-row operators,
+ * dense or nonlinear grid children, K > 4, arrays not aligned like their scalar. */
 typedef struct jh_chain jh_chain;
 typedef enum { JH_CHAIN_FORWARD = 0, JH_CHAIN_ADJOINT = 1, JH_CHAIN_NORMAL = 2 } jh_chain_type;
 typedef enum { JH_STAGE_SCALE = 1, JH_STAGE_DIAG = 2 } jh_stage_kind;
@@ -593,7 +604,7 @@ int jh_team_normal_mul(int n, const jh_blockop *const *ops, jh_bvec *const *ys, 
  * aligned loads of diagonals laid out like the range vector: -1 rows of 64 KiB or more, 0 never, 1 always; same bits), "tall_f" (F(m) of a tall nonlinear operator of elementwise children -- jh_blockop_f -- on the tall tiling: 1 yes, 0 the
  * general kernels; same bits), "dense_list_shared" (round 6: the rows pass of y = B x for DENSE children whose columns are off the 16-byte grid numbers its
  * chunks XCD by XCD and loads temporally, so the 128-byte line two neighbouring rows share is fetched from HBM once: 1 yes, 0 round 5's pass; same bits),
- * "dense_list_rl_min" (log2 of the fewest row lanes per workgroup of that pass, 0: automatic), "red_blocks_wave" (round 6: jh_norm_blocks / jh_dot_blocks of many blocks of at most 16 KiB with a wave per block in one launch: 1 yes, 0 a workgroup per block + the fold; within the reductions' tolerance of each other), "adj_bare_chain" (round 6: jh_blockop_mul_adj and jh_blockop_normal_mul of a tall operator with rows of several kinds, or rows off the 16-byte grid, of up to 4 MiB on the chain kernels with empty stage lists -- packed row records --: 1 yes, 0 the MIXED tall kernel; same bits unless the split walk's part count changes), "adj_thin_mixed" (round 6: the adjoint of a tall operator with rows of several kinds on thin workgroups when fat ones would leave CUs idle -- rows of 1-8 MiB --: 1 yes, 0 round 5's shapes; same bits unless the split walk's part count changes), "grid_normal" (round 6: jh_blockop_normal_mul on N x (2 .. 4) grids of equal elementwise blocks -- diagonals, zero / identity / scalar blocks -- in one pass: 1 yes, 2 grids of plain diagonals only, 0 JH_ERR_UNSUPPORTED as before; same bits), "dense_combine" (round 6: operators whose non-zero blocks are
+ * "dense_list_rl_min" (log2 of the fewest row lanes per workgroup of that pass, 0: automatic), "red_blocks_wave" (round 6: jh_norm_blocks / jh_dot_blocks of many blocks of at most 16 KiB with a wave per block in one launch: 1 yes, 0 a workgroup per block + the fold; within the reductions' tolerance of each other), "adj_bare_chain" (round 6: jh_blockop_mul_adj and jh_blockop_normal_mul of a tall operator with rows of several kinds, or rows off the 16-byte grid, of up to 4 MiB on the chain kernels with empty stage lists -- packed row records --: 1 yes, 0 the MIXED tall kernel; same bits unless the split walk's part count changes), "adj_thin_mixed" (round 6: the adjoint of a tall operator with rows of several kinds on thin workgroups when fat ones would leave CUs idle -- rows of 1-8 MiB --: 1 yes, 0 round 5's shapes; same bits unless the split walk's part count changes), "grid_normal" (round 6: jh_blockop_normal_mul on N x (2 .. 4) grids of equal elementwise blocks -- diagonals, zero / identity / scalar blocks -- in one pass: 1 yes, 2 grids of plain diagonals only, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_chain" (jh_chain_create on N x (2 .. 4) grids of equal elementwise blocks -- fused chains A' o W o A, (W o A)', W o A through a multi-parameter operator: 1 yes, 0 JH_ERR_UNSUPPORTED as before, the caller runs the composite stage by stage; same bits), "dense_combine" (round 6: operators whose non-zero blocks are
  * all DENSE children sum the products of a block line from CSR lists in one launch: 1 yes, 0 the general step lists; same bits);
  * round 4: "cg_dev" (jh_cgls_solve / jh_cgnr_solve with the recurrences on the device, graph-replayed unless lsqr_graph = 0: 1 automatic -- CGLS
  * like lsqr_graph, CG through the fused A'A up to 2 GiB of coefficients --, 2 at any size, 0 never: the host loops; within solver tolerance
@@ -616,7 +627,7 @@ int jh_team_normal_mul(int n, const jh_blockop *const *ops, jh_bvec *const *ys, 
  * "small_loop_max_kib" (operators of SMALL dense children whose matrices together reach this many KiB take
  * the list route instead of the one-launch loop: 512);
  * jh_tune_get also reads the counters "last_fwd_walk" (grid walk of the latest tall forward: 0 sequential, 1 all rows, 2 column bands),
- * "last_fwd_rows_per_wg", "last_adj_launches", "last_adj_parts", "last_step_chain" (row chunks of the latest one-pass step, 0: the plain walk), "graph_replays", "last_lsqr_graph" / "last_cg_graph" (graph replays of the latest
+ * "last_fwd_rows_per_wg", "last_adj_launches", "last_adj_parts", "last_grid_chain_shape" (how the latest grid chain was launched: see jh_chain_create), "last_step_chain" (row chunks of the latest one-pass step, 0: the plain walk), "graph_replays", "last_lsqr_graph" / "last_cg_graph" (graph replays of the latest
  * jh_lsqr_solve / jh_cgls_solve or jh_cgnr_solve; 0: the host loop ran) and "last_dense_fused" (1: the latest dense adjoint / wide forward took the
  * fused launch). */
 int jh_tune_set(const char *name, int64_t value);

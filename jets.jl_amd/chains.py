@@ -33,13 +33,15 @@ _UNSUPPORTED = 4        # JH_ERR_UNSUPPORTED
 ENABLED = [True]        # tests / A-B timings: [False] sends every composite and sum down the stage-by-stage path of rounds 1-5
 STATS = {"chain_calls": 0, "sum_terms_fused": 0, "bcast_calls": 0,    # how often a fused run was applied (tests assert that the fused path is the one that ran)
          "chain_range_calls": 0,                                      # ... and how often one ran on an element range of the domain (rowpart's pipelined exchange)
-         "chain_step_calls": 0, "chain_solve_calls": 0}               # the solvers on a FORWARD chain: one-pass steps (jh_chain_bidiag_step), whole native solves (jh_*_solve_chain)
+         "chain_step_calls": 0, "chain_solve_calls": 0,               # the solvers on a FORWARD chain: one-pass steps (jh_chain_bidiag_step), whole native solves (jh_*_solve_chain)
+         "grid_chain_calls": 0}                                       # fused runs through an N x (2 .. 4) grid (also counted in chain_calls / chain_solve_calls)
 
 
 # ------------------------------------------------------------------------------ classification -----
 class Stage:
-    """One stage of a chain as the planner sees it.  kind: 'tall' (a tall native block operator or its adjoint), 'scale', 'diag'
-    (coefficients in one device vector), 'rows' (a block-diagonal block operator: per-row coefficient arrays), 'identity', 'opaque'."""
+    """One stage of a chain as the planner sees it.  kind: 'tall' (a tall native block operator or its adjoint), 'grid' (an N x (2 .. 4)
+    native block operator or its adjoint: jh_grid_chain.hip), 'scale', 'diag' (coefficients in one device vector), 'rows' (a block-diagonal
+    block operator: per-row coefficient arrays), 'identity', 'opaque'.  'tall' and 'grid' both anchor a fused run (Stage.anchors)."""
 
     __slots__ = ("kind", "op", "R", "base", "nat", "adj", "a", "flags", "vec", "conj", "ptrs", "row_flags", "keep")
 
@@ -51,6 +53,9 @@ class Stage:
     def elementwise(self) -> bool:
         return self.kind in ("scale", "diag", "rows", "identity")
 
+    def anchors(self) -> bool:
+        return self.kind in ("tall", "grid")
+
     def signature(self):
         if self.kind == "scale":
             return ("s", self.a, self.flags)
@@ -58,8 +63,8 @@ class Stage:
             return ("d", self.vec.ptr, self.vec.length(), bool(self.conj))
         if self.kind == "rows":
             return ("r", tuple(self.ptrs), bytes(self.row_flags), bool(self.conj))
-        if self.kind == "tall":
-            return ("t", self.nat.serial, bool(self.adj))
+        if self.kind in ("tall", "grid"):
+            return (self.kind[0], self.nat.serial, bool(self.adj))
         return (self.kind,)
 
 
@@ -155,6 +160,9 @@ def classify(op: Jop, R) -> Stage:
     rows = _blockdiag_rows(base)
     if rows is not None:
         return Stage("rows", op, R, ptrs=rows[0], row_flags=rows[1], keep=rows[2], conj=adj)
+    nat = _b._grid_native(base) if nat is None else None           # (a block-DIAGONAL square operator stays the weights stage above)
+    if nat is not None:
+        return Stage("grid", op, R, base=base, nat=nat, adj=adj)     # (the library declines block kinds it has no kernel for: stage by stage then)
     return Stage("opaque", op, R)
 
 
@@ -167,8 +175,10 @@ class ChainHandle:
     def __init__(self, tall: Stage, ctype: int, pre: Sequence[Stage], mid: Sequence[Stage], post: Sequence[Stage]):
         self._keep = [tall.nat]
         self._h = C.c_void_p()
+        self.grid = tall.kind == "grid"
         nrow = tall.base.jet.s["ops"].shape[0]
-        nblk = domain(tall.base).length()
+        ndom = domain(tall.base).length()                 # (a grid's domain is its K blocks: K n elements)
+        nblk = range_(tall.base).length() // nrow         # one block row of the range
         es = np.dtype(domain(tall.base).eltype()).itemsize
 
         def pack(stages, range_side):
@@ -182,7 +192,7 @@ class ChainHandle:
                 if st.kind == "diag":
                     self._keep.append(st.vec)
                     n = nrow if range_side else 1
-                    want = nblk * n
+                    want = nblk * n if range_side else ndom
                     if st.vec.length() != want:
                         raise JetsHipError(_UNSUPPORTED, f"a diagonal of {st.vec.length()} elements on a side of {want}")
                     # (one pointer per block row of a slab: numpy, not a Python loop -- a composite built anew for every application pays this per call,
@@ -272,7 +282,7 @@ def _segments(st: Sequence[Stage]):
         j = i
         while j < n and st[j].elementwise():
             j += 1
-        if j < n and st[j].kind == "tall":
+        if j < n and st[j].anchors():
             t = st[j]
             if not t.adj:                                     # E* A E* [A' E*]
                 pre = _active(st[i:j])
@@ -284,13 +294,16 @@ def _segments(st: Sequence[Stage]):
                 while k < n and st[k].elementwise() and len(_active(st[j + 1:k + 1])) <= MAX_STAGES:
                     k += 1
                 mid = _active(st[j + 1:k])
-                if k < n and st[k].kind == "tall" and st[k].adj and st[k].nat is t.nat:
+                pair = k < n and st[k].kind == t.kind and st[k].adj and st[k].nat is t.nat
+                if pair:
                     l = k + 1
                     while l < n and st[l].elementwise() and len(_active(st[k + 1:l + 1])) <= MAX_STAGES:
                         l += 1
-                    steps.append(("chain", CHAIN_NORMAL, t, pre, mid, _active(st[k + 1:l]), i, l - 1))
+                    post = _active(st[k + 1:l])
+                if pair and (t.kind == "tall" or pre or mid or post):
+                    steps.append(("chain", CHAIN_NORMAL, t, pre, mid, post, i, l - 1))
                     i = l
-                elif pre or mid:
+                elif pre or mid:                              # (a bare (A', A) of a grid keeps jh_blockop_normal_mul: k_grid_normal)
                     steps.append(("chain", CHAIN_FORWARD, t, pre, mid, [], i, k - 1))
                     i = k
                 else:
@@ -450,13 +463,15 @@ def stages_of(op: Jop):
     return [(JopLn(o), range_(JopLn(o))) for o in reversed(_j.jops_comp(op))]
 
 
-def one_run(stages: Sequence, cache: ChainCache, tag, ctype: int, make: bool = True):
+def one_run(stages: Sequence, cache: ChainCache, tag, ctype: int, make: bool = True, grid: bool = True):
     """When the WHOLE stage list is one fused run of chain type `ctype`: its ChainHandle (make=True; None when the library declines) or True
-    (make=False: planned, no handle built).  None otherwise."""
+    (make=False: planned, no handle built).  None otherwise.  grid=False: not a run through a grid (the row partition has no grid chains)."""
     if not ENABLED[0]:
         return None
     steps = plan(stages, cache, tag)
     if len(steps) != 1 or steps[0][0] != "chain" or steps[0][1] != ctype:
+        return None
+    if not grid and steps[0][2].kind == "grid":
         return None
     if not make:
         return True
@@ -512,6 +527,8 @@ def run(out, x, stages: Sequence, ws, cache: ChainCache | None, tag, accumulate:
                     h.apply(dst, cur, accumulate if last else 0)
                     done = True
                     STATS["chain_calls"] += 1
+                    if tall.kind == "grid":
+                        STATS["grid_chain_calls"] += 1
                 except JetsHipError as e:
                     if e.status != _UNSUPPORTED:
                         raise
@@ -554,7 +571,7 @@ def _overwrites(op: Jop, transposed: bool) -> bool:
         if isinstance(base, JopLn) and base.jet.f in (_j.JetSum_f, _j.JetComposite_f):
             return True
         st = classify(adjoint(base), None)
-        return st.kind in ("scale", "diag", "identity") or (st.kind == "tall")      # the tall adjoint zeroes m first (1042)
+        return st.kind in ("scale", "diag", "identity") or st.anchors()      # the tall / grid adjoint zeroes m first (1042: N >= 2 rows)
     return _b.overwrites_its_whole_range(JopLn(op)) or classify(JopLn(op), None).kind in ("scale", "diag", "identity")
 
 
@@ -631,6 +648,8 @@ class SolverChains:
     """The fused routes of the one-GPU solvers (lsqr.py, cgls.py) on a composite L = R o A o P that the planner turns into ONE FORWARD run
     (W o A, a block-diagonal @blockop of weights o A, W o A o M, a * (W o A)): `fwd` is its ChainHandle -- the Golub-Kahan step
     (jh_chain_bidiag_step) and the native solves (jh_*_solve_chain) take it --, `normal()` the NORMAL chain of adjoint(L) o L (cgnr_core's hook).
+    Through an N x K grid (fwd.grid) there is no one-pass step: step() declines without calling the library, LSQR / CGLS keep their two
+    passes (two fused grid chains), CGNR takes jh_cgnr_solve_chain or the NORMAL hook.
     fwd is None when L is not one such run, the library declines, or JETS_CHAIN_STEP=0 (today's route: the chain into a range temporary, then
     the ADJOINT chain)."""
 
@@ -651,6 +670,8 @@ class SolverChains:
     def step(self, u, v, w, alpha: float, beta: float):
         """u <- alpha L v + beta u ; w <- L'u ; returns ||u||^2, or None when the library declines (R and R^H above four stages: the caller
         keeps the two halves)."""
+        if self.fwd.grid:
+            return None
         out = C.c_double(0)
         try:
             check(lib.jh_chain_bidiag_step(self.fwd.handle, u.handle, v.handle, w.handle, float(alpha), float(beta), C.byref(out)))

@@ -1,0 +1,40 @@
+// jh_grid_chain.hip -- the FORWARD instantiations of k_grid_chain (jh_grid_chain_kernels.h: fused chains through an N x K grid), and the grid
+// side of the chain handle: the checks jh_chain_create makes before it builds a grid chain.  ADJOINT and NORMAL live in jh_grid_chain_adj.hip and
+// jh_grid_chain_nrm.hip, as the tall chains' do (build time).
+#include "jh_grid_chain_kernels.h"
+
+namespace jhb {
+int grid_chain_launch_adjoint(const jh_chain *ch, int prog, void *out, const void *in, int accumulate);   // jh_grid_chain_adj.hip
+int grid_chain_launch_normal(const jh_chain *ch, int prog, void *out, const void *in, int accumulate);    // jh_grid_chain_nrm.hip
+
+// may jh_chain_create build a grid chain on `op`?  An N x K grid, N >= 2, K = 2 .. 4, of equal blocks of >= 16 bytes, every block a diagonal, an
+// adjointed diagonal, a zero, an identity or a scalar (the kinds of k_grid_normal_mixed), no nonlinear child, coefficients aligned like their scalar;
+// knob grid_chain = 1
+bool grid_chain_ok(const jh_blockop *op)
+{
+    if (jh_ctx().grid_chain == 0) return false;
+    if (op->tall || op->nrow < 2 || op->ncol < 2 || op->ncol > 4 || !op->uniform_rows || !op->elementwise || op->nonlinear || op->wide_scale) return false;
+    for (const jh_block_desc &b : op->blocks)
+        if (b.kind != JH_OP_ZERO && b.kind != JH_OP_IDENTITY && b.kind != JH_OP_SCALE && b.kind != JH_OP_DIAG) return false;
+    const int64_t n = op->row_len[0];
+    if (n * (int64_t)jh_dtype_size(op->dtype) < 16) return false;
+    for (int64_t v : op->col_len)
+        if (v != n) return false;
+    return op->coeff_scalar_aligned;
+}
+
+// vectors aligned like their scalar (the under-aligned packs of jh_blockop_common.h take any such address)
+bool grid_chain_vectors_ok(const jh_blockop *op, const void *a, const void *b)
+{
+    const size_t es = jh_dtype_size(op->dtype), sa = jh_dtype_complex(op->dtype) ? es / 2 : es;
+    return ((((uintptr_t)a) | ((uintptr_t)b)) & (sa - 1)) == 0 && op->coeff_scalar_aligned;
+}
+
+// out = chain(in) for chain type `type` over program `prog` (GRID_PROG_OWN: the handle's own; GRID_PROG_ADJ / _NRM: derived from a FORWARD chain)
+int grid_chain_launch(const jh_chain *ch, int prog, int type, void *out, const void *in, int accumulate)
+{
+    if (type == JH_CHAIN_ADJOINT) return grid_chain_launch_adjoint(ch, prog, out, in, accumulate);
+    if (type == JH_CHAIN_NORMAL) return grid_chain_launch_normal(ch, prog, out, in, accumulate);
+    return launch_grid_chain<0>(ch, prog, out, in, accumulate);
+}
+}  // namespace jhb

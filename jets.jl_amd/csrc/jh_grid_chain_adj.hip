@@ -1,0 +1,10 @@
+// jh_grid_chain_adj.hip -- the ADJOINT instantiations of k_grid_chain (jh_grid_chain_kernels.h), a translation unit of their own (build time: see
+// jh_tall_chain.hip).
+#include "jh_grid_chain_kernels.h"
+
+namespace jhb {
+int grid_chain_launch_adjoint(const jh_chain *ch, int prog, void *out, const void *in, int accumulate)
+{
+    return launch_grid_chain<1>(ch, prog, out, in, accumulate);
+}
+}  // namespace jhb

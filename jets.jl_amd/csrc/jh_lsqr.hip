@@ -1629,10 +1629,10 @@ extern "C" int jh_cgnr_solve_team(int n, const jh_blockop *const *ops, jh_bvec *
 // ------------------------------------------------------------------ the solvers on a FORWARD chain (weighted least squares) ---------------
 // lsqr(W o A o M, b) and its siblings (docs/src/index.md:235-246): the loops above with the four passes of the chain (Passes), one GPU, host-driven
 // at every size.  Declined (JH_ERR_UNSUPPORTED) before anything is touched where the step is: the caller keeps its generic loop.
-static int chain_solver_args(const jh_chain *fwd, const jh_bvec *u, const jh_bvec *x, const jh_blockop **op, const char *fn)
+static int chain_solver_args(const jh_chain *fwd, const jh_bvec *u, const jh_bvec *x, const jh_blockop **op, const char *fn, bool needs_step = true)
 {
     JH_REQUIRE(fwd && u && x, "%s: null argument", fn);
-    JH_TRY(jhb::chain_solver_ok(fwd, u, x, op));
+    JH_TRY(jhb::chain_solver_ok(fwd, u, x, op, needs_step));
     JH_TRY(jh_enter(*op, u, x));
     return JH_OK;
 }
@@ -1657,6 +1657,6 @@ extern "C" int jh_cgnr_solve_chain(const jh_chain *fwd, jh_bvec *b, jh_bvec *x, 
                                    int force_maxiter, jh_lsqr_result *res, double *history)
 {
     const jh_blockop *op = nullptr;
-    JH_TRY(chain_solver_args(fwd, b, x, &op, "jh_cgnr_solve_chain"));
+    JH_TRY(chain_solver_args(fwd, b, x, &op, "jh_cgnr_solve_chain", false));   // (the ADJOINT and NORMAL programs only: a grid chain takes it too)
     return cgnr_impl(1, &op, &b, &x, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history, Exch::none, fwd);
 }

@@ -9,6 +9,9 @@ namespace jhb {
 int chain_launch_adjoint(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem, const ChainArgs *ca = nullptr);   // jh_tall_chain_adj.hip
 int chain_launch_normal(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem, const ChainArgs *ca = nullptr);    // jh_tall_chain_nrm.hip
 int chain_launch_step(const jh_chain *ch, const ChainArgs &ca, void *u, const void *v, void *w, double alpha, double beta, double *normsq);   // jh_tall_chain_step.hip
+bool grid_chain_ok(const jh_blockop *op);                                                                     // jh_grid_chain.hip
+bool grid_chain_vectors_ok(const jh_blockop *op, const void *a, const void *b);
+int grid_chain_launch(const jh_chain *ch, int prog, int type, void *out, const void *in, int accumulate);   // prog: 0 own, 1 / 2 the derived ADJOINT / NORMAL
 }  // namespace jhb
 
 namespace {
@@ -97,19 +100,26 @@ void derive_progs(jh_chain *ch)
     ch->nrm_args = nrm;
 }
 
-// word 0 of every record from the operator's blocks as they are NOW, then the table to the device (at create, and again when jh_blockop_point has
+// are the vectors (and the operator's coefficients) aligned as the chain's kernels need them?  (NULL: not checked)
+bool chain_vectors_ok(const jh_chain *ch, const void *rng, const void *dom)
+{
+    return ch->ncol > 1 ? jhb::grid_chain_vectors_ok(ch->op, rng, dom) : jhb::tall_unaligned_ok(ch->op, rng, dom);
+}
+
+// word 0 (a grid: words 0 .. K-1) of every record from the operator's blocks as they are NOW, then the table to the device (at create, and again when jh_blockop_point has
 // moved the SQUARE rows' arrays since)
 int chain_sync_rows(jh_chain *ch)
 {
     const jh_blockop *op = ch->op;
-    const size_t rw = (size_t)(1 + ch->nw);
-    for (int64_t i = 0; i < op->nrow; i++) {
-        const jh_block_desc &b = op->blocks[(size_t)i];
-        const jh_dev_block db = jh_dev_block_of(b);
-        const uint64_t p = (uint64_t)(uintptr_t)b.coeff;
-        JH_REQUIRE((p >> 48) == 0, "fused chain: a coefficient address does not fit 48 bits");
-        ch->host_tab[(size_t)i * rw] = p | ((uint64_t)(b.kind & 7) << 48) | ((uint64_t)(b.adjoint ? 1 : 0) << 51) | ((uint64_t)(db.real_scale ? 1 : 0) << 52);
-    }
+    const size_t rw = (size_t)(ch->ncol + ch->nw);
+    for (int64_t i = 0; i < op->nrow; i++)
+        for (int k = 0; k < ch->ncol; k++) {
+            const jh_block_desc &b = op->blocks[(size_t)(i + k * op->nrow)];             // (the block table is column-major)
+            const jh_dev_block db = jh_dev_block_of(b);
+            const uint64_t p = (uint64_t)(uintptr_t)(ch->ncol == 1 || b.kind == JH_OP_DIAG ? b.coeff : nullptr);
+            JH_REQUIRE((p >> 48) == 0, "fused chain: a coefficient address does not fit 48 bits");
+            ch->host_tab[(size_t)i * rw + (size_t)k] = p | ((uint64_t)(b.kind & 7) << 48) | ((uint64_t)(b.adjoint ? 1 : 0) << 51) | ((uint64_t)(db.real_scale ? 1 : 0) << 52);
+        }
     JH_CHECK_HIP(hipMemcpyAsync(ch->dev_tab, ch->host_tab.data(), ch->host_tab.size() * sizeof(uint64_t), hipMemcpyHostToDevice, jh_ctx().stream));
     JH_CHECK_HIP(hipStreamSynchronize(jh_ctx().stream));
     ch->op_gen = op->table_gen;
@@ -131,7 +141,7 @@ int chain_check(const jh_chain *ch, const jh_bvec *out, const jh_bvec *x, int ac
         return jh_fail(JH_ERR_STATE, "%s: operator has nonlinear blocks and no linearisation point (jh_blockop_point)", fn);
     const void *rng = ch->type == JH_CHAIN_FORWARD ? out->data : (ch->type == JH_CHAIN_ADJOINT ? x->data : nullptr);
     const void *dom = ch->type == JH_CHAIN_FORWARD ? x->data : out->data;
-    if (!jhb::tall_unaligned_ok(op, rng, dom) || (ch->type == JH_CHAIN_NORMAL && !jhb::tall_unaligned_ok(op, nullptr, x->data)))
+    if (!chain_vectors_ok(ch, rng, dom) || (ch->type == JH_CHAIN_NORMAL && !chain_vectors_ok(ch, nullptr, x->data)))
         return jh_fail(JH_ERR_UNSUPPORTED, "%s: a vector or coefficient array is not aligned like its scalar", fn);
     return JH_OK;
 }
@@ -148,14 +158,17 @@ int jh_chain_create(const jh_blockop *op, int type, int npre, const jh_chain_sta
     JH_REQUIRE(type == JH_CHAIN_FORWARD || type == JH_CHAIN_ADJOINT || type == JH_CHAIN_NORMAL, "jh_chain_create: unknown chain type %d", type);
     JH_REQUIRE(!(type == JH_CHAIN_FORWARD && npost) && !(type == JH_CHAIN_ADJOINT && npre),
                "jh_chain_create: a FORWARD chain has no stages after A', an ADJOINT chain none before A");
-    if (!(op->tall && op->uniform_rows && op->elementwise) || op->nrow < 2 || op->row_len[0] * (int64_t)jh_dtype_size(op->dtype) < 16)
-        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_create: needs a tall operator of >= 2 equal elementwise rows of at least 16 bytes");
+    const bool grid = jhb::grid_chain_ok(op);
+    if (!grid && (!(op->tall && op->uniform_rows && op->elementwise) || op->nrow < 2 || op->row_len[0] * (int64_t)jh_dtype_size(op->dtype) < 16))
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_create: needs a tall operator of >= 2 equal elementwise rows of at least 16 bytes, or an N x (2 .. 4) grid "
+                                           "of equal diagonal / zero / identity / scalar blocks (knob grid_chain)");
     const size_t es = jh_dtype_size(op->dtype);
     const size_t sa = jh_dtype_complex(op->dtype) ? es / 2 : es;
     jh_chain *ch = new jh_chain();
     ch->ctx = op->ctx;
     ch->op = op;
     ch->type = type;
+    ch->ncol = grid ? (int)op->ncol : 1;
     std::vector<const jh_chain_stage *> s_pre, s_mid, s_post;
     int st = build_prog("domain-side (before A)", npre, pre, op->dtype, 1, ch->args.pre, s_pre);
     if (st == JH_OK) st = build_prog("range-side", nmid, mid, op->dtype, op->nrow, ch->args.mid, s_mid);
@@ -169,7 +182,7 @@ int jh_chain_create(const jh_blockop *op, int type, int npre, const jh_chain_sta
     for (size_t q = 0; q < s_pre.size(); q++) { ch->args.pre_c[q] = s_pre[q]->coeff[0]; note(s_pre[q]->coeff[0]); }
     for (size_t q = 0; q < s_post.size(); q++) { ch->args.post_c[q] = s_post[q]->coeff[0]; note(s_post[q]->coeff[0]); }
     ch->nw = (int)s_mid.size();
-    const size_t rw = (size_t)(1 + ch->nw);
+    const size_t rw = (size_t)(ch->ncol + ch->nw);
     ch->host_tab.assign(rw * (size_t)op->nrow, 0);
     for (int w = 0; w < ch->nw; w++)
         for (int64_t i = 0; i < op->nrow; i++) {
@@ -177,7 +190,7 @@ int jh_chain_create(const jh_blockop *op, int type, int npre, const jh_chain_sta
             const uint64_t fl = s_mid[(size_t)w]->row_flags ? (s_mid[(size_t)w]->row_flags[i] & 3u) : 0u;
             note(p);
             if (((uint64_t)(uintptr_t)p) >> 48) scalar_aligned = false;           // (a device address above 2^48 does not exist on this platform)
-            ch->host_tab[(size_t)i * rw + 1 + (size_t)w] = (uint64_t)(uintptr_t)p | (fl << 48);
+            ch->host_tab[(size_t)i * rw + (size_t)ch->ncol + (size_t)w] = (uint64_t)(uintptr_t)p | (fl << 48);
         }
     if (!scalar_aligned) { delete ch; return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_create: a coefficient array is not aligned like its scalar"); }
     hipError_t e = jh_device_malloc(jh_ctx().device, (void **)&ch->dev_tab, ch->host_tab.size() * sizeof(uint64_t));
@@ -190,8 +203,20 @@ int jh_chain_create(const jh_blockop *op, int type, int npre, const jh_chain_sta
         const int st2 = chain_sync_rows(ch);
         if (st2 != JH_OK) { (void)hipFree(ch->dev_tab); delete ch; return st2; }
     }
-    ch->stream_bytes = (double)op->nrow * (double)op->row_len[0] * (double)es * (double)(1 + ch->nw);
+    ch->stream_bytes = (double)op->nrow * (double)op->row_len[0] * (double)es * (double)(ch->ncol + ch->nw);
     if (type == JH_CHAIN_FORWARD) derive_progs(ch);
+    if (ch->ncol > 1) {
+        const ChainProg mids[3] = {ch->args.mid, ch->adj_args.mid, ch->nrm_args.mid};
+        hipError_t e2 = jh_device_malloc(jh_ctx().device, (void **)&ch->dev_mid, sizeof(mids));
+        if (e2 == hipSuccess) e2 = hipMemcpyAsync(ch->dev_mid, mids, sizeof(mids), hipMemcpyHostToDevice, jh_ctx().stream);
+        if (e2 == hipSuccess) e2 = hipStreamSynchronize(jh_ctx().stream);
+        if (e2 != hipSuccess) {
+            if (ch->dev_mid) (void)hipFree(ch->dev_mid);
+            (void)hipFree(ch->dev_tab);
+            delete ch;
+            return jh_fail(e2 == hipErrorOutOfMemory ? JH_ERR_NOMEM : JH_ERR_HIP, "jh_chain_create: %s", hipGetErrorString(e2));
+        }
+    }
     jh_handle_born(ch->ctx);
     *out = ch;
     return JH_OK;
@@ -202,6 +227,7 @@ int jh_chain_destroy(jh_chain *ch)
     if (!ch) return JH_OK;
     jh_quiesce_scope quiet(ch->ctx);
     if (ch->dev_tab) (void)hipFree(ch->dev_tab);
+    if (ch->dev_mid) (void)hipFree(ch->dev_mid);
     jh_handle_died(ch->ctx);
     delete ch;
     return JH_OK;
@@ -214,6 +240,7 @@ int jh_chain_apply(const jh_chain *ch, jh_bvec *out, const jh_bvec *x, int accum
     JH_TRY(jh_enter(op, out, x));
     JH_TRY(chain_check(ch, out, x, accumulate, "jh_chain_apply"));
     if (ch->op_gen != op->table_gen) JH_TRY(chain_sync_rows(const_cast<jh_chain *>(ch)));   // (the operator was pointed again: its SQUARE rows' arrays moved)
+    if (ch->ncol > 1) return jhb::grid_chain_launch(ch, 0, ch->type, out->data, x->data, accumulate);
     const int64_t n = op->row_len[0];
     if (ch->type == JH_CHAIN_ADJOINT) return jhb::chain_launch_adjoint(ch, out->data, x->data, accumulate, 0, out->length);
     if (ch->type == JH_CHAIN_NORMAL) return jhb::chain_launch_normal(ch, out->data, x->data, accumulate, 0, out->length);
@@ -238,6 +265,7 @@ int jh_chain_apply_range(const jh_chain *ch, jh_bvec *out, const jh_bvec *x, int
     JH_TRY(jh_enter(op, out, x));
     if (ch->type == JH_CHAIN_FORWARD)
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_apply_range: a FORWARD chain needs no exchange (each rank's rows depend on the replicated domain vector alone)");
+    if (ch->ncol > 1) return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_apply_range: a grid chain has no ranged form (apply the whole vector)");
     JH_TRY(chain_check(ch, out, x, accumulate, "jh_chain_apply_range"));
     JH_REQUIRE(first_elem >= 0 && count >= 0 && first_elem <= out->length - count,
                "jh_chain_apply_range: elements [%lld, %lld) outside the domain vector (%lld elements)", (long long)first_elem,
@@ -277,6 +305,7 @@ int jh_chain_bidiag_step(const jh_chain *fwd, jh_bvec *u, const jh_bvec *v, jh_b
 {
     JH_REQUIRE(fwd && u && v && w, "jh_chain_bidiag_step: null argument");
     JH_REQUIRE(fwd->type == JH_CHAIN_FORWARD, "jh_chain_bidiag_step: needs a FORWARD chain (got type %d)", fwd->type);
+    if (fwd->ncol > 1) return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step: a grid chain has no one-pass step (run the FORWARD chain, then the ADJOINT)");
     if (!fwd->nrm_ok)
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step: R and R^H need more than %d range-side stages", JH_CHAIN_MAX_STAGES);
     const jh_blockop *op = fwd->op;
@@ -307,9 +336,10 @@ int chain_apply_derived(const jh_chain *fwd, int which, jh_bvec *out, const jh_b
     const int64_t nrange = op->row_off[(size_t)op->nrow], ndom = op->col_off[(size_t)op->ncol];
     JH_REQUIRE(out->dtype == op->dtype && in->dtype == op->dtype && out->data != in->data, "chain_apply_derived: dtype mismatch or aliasing");
     JH_REQUIRE(out->length == ndom && in->length == (which == JH_CHAIN_ADJOINT ? nrange : ndom), "chain_apply_derived: vector lengths");
-    const bool ok = which == JH_CHAIN_ADJOINT ? jhb::tall_unaligned_ok(op, in->data, out->data)
-                                              : jhb::tall_unaligned_ok(op, nullptr, out->data) && jhb::tall_unaligned_ok(op, nullptr, in->data);
+    const bool ok = which == JH_CHAIN_ADJOINT ? chain_vectors_ok(fwd, in->data, out->data)
+                                              : chain_vectors_ok(fwd, nullptr, out->data) && chain_vectors_ok(fwd, nullptr, in->data);
     if (!ok) return jh_fail(JH_ERR_UNSUPPORTED, "chain_apply_derived: a vector is not aligned like its scalar");
+    if (fwd->ncol > 1) return grid_chain_launch(fwd, which == JH_CHAIN_ADJOINT ? 1 : 2, which, out->data, in->data, 0);
     if (which == JH_CHAIN_ADJOINT) return chain_launch_adjoint(fwd, out->data, in->data, 0, 0, out->length, &fwd->adj_args);
     return chain_launch_normal(fwd, out->data, in->data, 0, 0, out->length, &fwd->nrm_args);
 }
@@ -317,16 +347,18 @@ int chain_apply_derived(const jh_chain *fwd, int which, jh_bvec *out, const jh_b
 
 namespace jhb {
 // may the solver loops run on this chain (jh_*_solve_chain)?  The checks of jh_chain_bidiag_step on the solver's vectors, before anything is touched
-int chain_solver_ok(const jh_chain *fwd, const jh_bvec *u, const jh_bvec *x, const jh_blockop **op)
+int chain_solver_ok(const jh_chain *fwd, const jh_bvec *u, const jh_bvec *x, const jh_blockop **op, bool needs_step)
 {
     JH_REQUIRE(fwd->type == JH_CHAIN_FORWARD, "jh_*_solve_chain: needs a FORWARD chain (got type %d)", fwd->type);
+    if (needs_step && fwd->ncol > 1)
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_*_solve_chain: a grid chain has no one-pass step (LSQR / CGLS keep their two-pass loops; CGNR runs)");
     if (!fwd->nrm_ok)
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_*_solve_chain: R and R^H need more than %d range-side stages", JH_CHAIN_MAX_STAGES);
     const jh_blockop *o = fwd->op;
     const int64_t nrange = o->row_off[(size_t)o->nrow], ndom = o->col_off[(size_t)o->ncol];
     JH_REQUIRE(u->dtype == o->dtype && x->dtype == o->dtype && u->length == nrange && x->length == ndom,
                "jh_*_solve_chain: the right-hand side must be a range vector and x a domain vector of the chain's operator");
-    if (!tall_unaligned_ok(o, u->data, x->data))
+    if (!chain_vectors_ok(fwd, u->data, x->data))
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_*_solve_chain: a vector is not aligned like its scalar");
     *op = o;
     return JH_OK;

@@ -468,8 +468,9 @@ struct jh_chain {
     const jh_blockop *op = nullptr;          // borrowed: must outlive the chain
     int type = 0;
     ChainArgs args{};
+    int ncol = 1;                            // A's block columns: 1 a tall operator, 2 .. 4 an N x K grid (jh_grid_chain_kernels.h: K block words per row record)
     int nw = 0;                              // range-side coefficient streams
-    uint64_t *dev_tab = nullptr;             // the row table: nrow records of (1 + nw) words
+    uint64_t *dev_tab = nullptr;             // the row table: nrow records of (ncol + nw) words
     std::vector<uint64_t> host_tab;          // its host copy (word 0 of every record is rebuilt when the operator is pointed again: jh_blockop_point moves
     int64_t op_gen = -1;                     //  the SQUARE rows' arrays) and the operator's table generation it was built for
     bool coeff16 = true;                     // every coefficient array of the stages on the 16-byte grid
@@ -479,6 +480,7 @@ struct jh_chain {
     // row table and streams
     ChainArgs adj_args{}, nrm_args{}, step_args{};
     bool nrm_ok = false;                     // R + R^H fit one list (<= JH_CHAIN_MAX_STAGES stages)
+    ChainProg *dev_mid = nullptr;            // a grid chain: device copies of args.mid, adj_args.mid, nrm_args.mid (k_grid_chain reads its list per row)
 };
 
 namespace {

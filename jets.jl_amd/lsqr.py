@@ -374,6 +374,8 @@ def _count_chain_solve(chn):
         from . import chains as _chn
 
         _chn.STATS["chain_solve_calls"] += 1
+        if chn.fwd.grid:
+            _chn.STATS["grid_chain_calls"] += 1
 
 
 def _native_team_solve(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, force_maxiter):

@@ -250,8 +250,8 @@ class _ShardChains:
             self._nrm_op = compose(adjoint(L), L)
             self._adj = _chn.stages_of(adjoint(L))
             self._nrm = _chn.stages_of(self._nrm_op)
-        self.has_adj = self._adj is not None and _chn.one_run(self._adj, self.cache, "rowpart_adj", _chn.CHAIN_ADJOINT, make=False) is not None
-        self.has_normal = self._nrm is not None and _chn.one_run(self._nrm, self.cache, "rowpart_normal", _chn.CHAIN_NORMAL, make=False) is not None
+        self.has_adj = self._adj is not None and _chn.one_run(self._adj, self.cache, "rowpart_adj", _chn.CHAIN_ADJOINT, make=False, grid=False) is not None
+        self.has_normal = self._nrm is not None and _chn.one_run(self._nrm, self.cache, "rowpart_normal", _chn.CHAIN_NORMAL, make=False, grid=False) is not None
 
     def adjoint(self):
         """The ChainHandle of adjoint(L), or None (not one run; the library declined)."""

@@ -525,6 +525,11 @@ function tall_native(A::Jop, ::Type{T}) where {T}
     (A isa JopLn && jet(A).df! === JetBlock_df! && size(state(A).ops, 2) == 1) || return C_NULL
     native_handle(state(A).ops, T)
 end
+# the native handle of an N x (2 .. 4) block operator (a multi-parameter grid: fused chains through it, jh_grid_chain.hip), else C_NULL
+function grid_native(A::Jop, ::Type{T}) where {T}
+    (A isa JopLn && jet(A).df! === JetBlock_df! && 2 <= size(state(A).ops, 2) <= 4 && size(state(A).ops, 1) >= 2) || return C_NULL
+    native_handle(state(A).ops, T)
+end
 
 # ---------------------------------------------------------------- the hot path: ONE ccall per mul!
 # More specific methods of the reference's block loops (src/Jets.jl:988-1057) for device vectors; anything the device does
@@ -732,7 +737,7 @@ const _CHAIN_MAX_STAGES = 4
 _stages_df(ops) = Any[JopLn(ops[i]) for i = length(ops):-1:1]            # application order (530-534)
 _stages_df′(ops) = Any[JopLn(ops[i])' for i = 1:length(ops)]             # (536-540)
 
-# what a stage is: (kind = :tall / :scale / :diag / :identity / :opaque, ...)
+# what a stage is: (kind = :tall / :grid / :scale / :diag / :identity / :opaque, ...); n: a block's length, ndom: the domain's (a grid: K n)
 function _chain_stage(op::Jop, ::Type{T}) where {T}
     adj = op isa JopAdjoint
     base = adj ? op.op : op
@@ -752,10 +757,16 @@ function _chain_stage(op::Jop, ::Type{T}) where {T}
         return (kind=:diag, op=op, vec=state(base).diagonal, conj=adj)
     end
     h = tall_native(base, T)
-    (h != C_NULL && size(state(base).ops, 1) >= 2) && return (kind=:tall, op=op, h=h, adj=adj, nrow=size(state(base).ops, 1), n=length(domain(base)))
+    (h != C_NULL && size(state(base).ops, 1) >= 2) && return (kind=:tall, op=op, h=h, adj=adj, nrow=size(state(base).ops, 1), n=length(domain(base)), ndom=length(domain(base)))
+    if h == C_NULL
+        g = grid_native(base, T)                                        # (the library declines the block kinds it has no kernel for: stage by stage then)
+        nrow = size(state(base).ops, 1)
+        g != C_NULL && return (kind=:grid, op=op, h=g, adj=adj, nrow=nrow, n=length(range(base)) ÷ nrow, ndom=length(domain(base)))
+    end
     (kind=:opaque, op=op)
 end
 _elementwise(st) = st.kind === :scale || st.kind === :diag || st.kind === :identity
+_anchors(st) = st.kind === :tall || st.kind === :grid
 _active(sts) = [st for st in sts if st.kind !== :identity]
 
 # cut the stages into steps: (:chain, type, tall, pre, mid, post, first, last) or (:op, index)   (chains.py: _segments)
@@ -764,7 +775,7 @@ function _chain_segments(st::Vector)
     while i <= n
         j = i
         while j <= n && _elementwise(st[j]); j += 1; end
-        if j <= n && st[j].kind === :tall
+        if j <= n && _anchors(st[j])
             t = st[j]
             if !t.adj                                                   # E* A E* [A' E*]
                 while length(_active(st[i:j-1])) > _CHAIN_MAX_STAGES
@@ -774,10 +785,14 @@ function _chain_segments(st::Vector)
                 k = j + 1
                 while k <= n && _elementwise(st[k]) && length(_active(st[j+1:k])) <= _CHAIN_MAX_STAGES; k += 1; end
                 mid = _active(st[j+1:k-1])
-                if k <= n && st[k].kind === :tall && st[k].adj && st[k].h == t.h
-                    l = k + 1
+                pair = k <= n && st[k].kind === t.kind && st[k].adj && st[k].h == t.h
+                l = k + 1
+                if pair
                     while l <= n && _elementwise(st[l]) && length(_active(st[k+1:l])) <= _CHAIN_MAX_STAGES; l += 1; end
-                    push!(steps, (:chain, Cint(2), t, pre, mid, _active(st[k+1:l-1]), i, l - 1)); i = l
+                end
+                post = pair ? _active(st[k+1:l-1]) : Any[]
+                if pair && (t.kind === :tall || !isempty(pre) || !isempty(mid) || !isempty(post))   # (a bare (A', A) of a grid keeps jh_blockop_normal_mul)
+                    push!(steps, (:chain, Cint(2), t, pre, mid, post, i, l - 1)); i = l
                 elseif !isempty(pre) || !isempty(mid)
                     push!(steps, (:chain, Cint(0), t, pre, mid, Any[], i, k - 1)); i = k
                 else
@@ -849,9 +864,9 @@ function _bcast_tree(st::Vector, first::Int, stop::Int, x)
     e
 end
 
-# a diagonal before A / after A' lives on the domain (n elements), one after A / before A' on the range (nrow * n)
+# a diagonal before A / after A' lives on the domain (ndom elements: n, or K n for a grid), one after A / before A' on the range (nrow * n)
 function _chain_sides_ok(t, pre, mid, post)
-    for st in vcat(pre, post); (st.kind === :diag && length(st.vec) != t.n) && return false; end
+    for st in vcat(pre, post); (st.kind === :diag && length(st.vec) != t.ndom) && return false; end
     for st in mid; (st.kind === :diag && length(st.vec) != t.nrow * t.n) && return false; end
     true
 end
@@ -1014,7 +1029,7 @@ end
 # one whole Golub-Kahan step in one pass: u <- alpha*(A v) + beta*u ; w <- A'u ; returns ||u||   (3/5 of the bytes of the two halves)
 function bidiag_step!(u::BlockArray{T,<:HipArray{T}}, w::HipArray{T}, A::JopLn, v::HipArray{T}, alpha::Real, beta::Real) where {T}
     h = tall_native(A, T)
-    h == C_NULL && return bidiag_step!(u, w, _plan_chain(A, T), v, alpha, beta)
+    h == C_NULL && return bidiag_step!(u, w, _plan_chain(A, T; grid=false), v, alpha, beta)   # (a grid chain has no one-pass step)
     nrm2 = Ref{Cdouble}()
     check(ccall((:jh_blockop_bidiag_step, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ref{Cdouble}),
                 h, handle(u), handle(v), handle(w), alpha, beta, nrm2))
@@ -1023,7 +1038,7 @@ end
 # the same step over a FORWARD chain L = R ∘ A ∘ P (a weighted operator W ∘ A, W ∘ A ∘ M, a * (W ∘ A): the composite 530-540 in the solvers' loop
 # 1138-1154): u <- alpha*(L v) + beta*u ; w <- L'u ; ||u|| in ONE pass over A, the weights and u (jh_chain_bidiag_step)
 function bidiag_step!(u::BlockArray{T,<:HipArray{T}}, w::HipArray{T}, chain::Ptr{Cvoid}, v::HipArray{T}, alpha::Real, beta::Real) where {T}
-    chain == C_NULL && error("bidiag_step!: needs a tall block operator or a composite that is one fused FORWARD chain")
+    chain == C_NULL && error("bidiag_step!: needs a tall block operator or a composite that is one fused FORWARD chain through a tall operator (N x K grids have no one-pass step)")
     nrm2 = Ref{Cdouble}()
     check(ccall((:jh_chain_bidiag_step, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ref{Cdouble}),
                 chain, handle(u), handle(v), handle(w), alpha, beta, nrm2))
@@ -1032,13 +1047,15 @@ end
 
 # the FORWARD chain handle of a composite that plans to ONE fused run R ∘ A ∘ P (W ∘ A, W ∘ A ∘ M, a * (W ∘ A)), or C_NULL: what the solvers below take
 # in place of a tall block operator (jh_*_solve_chain)
-function _plan_chain(L::Jop, ::Type{T}) where {T}
+# grid = false: not a chain through an N x K grid (those have no one-pass Golub-Kahan step: jh_lsqr_solve_chain / jh_cgls_solve_chain decline them)
+function _plan_chain(L::Jop, ::Type{T}; grid::Bool=true) where {T}
     (L isa JopLn && jet(L).df! === JetComposite_df!) || return C_NULL
     ops = state(L).ops
     st = Any[_chain_stage(JopLn(ops[i]), T) for i = length(ops):-1:1]   # application order (530-534)
     steps = _chain_segments(st)
     (length(steps) == 1 && steps[1][1] === :chain && steps[1][2] == Cint(0)) || return C_NULL
     _, ctype, t, pre, mid, post, _, _ = steps[1]
+    (grid || t.kind !== :grid) || return C_NULL
     _chain_sides_ok(t, pre, mid, post) || return C_NULL
     _chain_handle(ctype, t, pre, mid, post, T)
 end
@@ -1049,8 +1066,9 @@ end
 struct jh_lsqr_result; istop::Int32; itn::Int32; r1norm::Cdouble; r2norm::Cdouble; anorm::Cdouble; acond::Cdouble; arnorm::Cdouble; xnorm::Cdouble; end
 function hip_lsqr!(x::HipArray{T}, A::JopLn, b::BlockArray{T,<:HipArray{T}}; x0::Bool=false, damp=0.0, atol=1e-6, btol=1e-6, conlim=1e8, maxiter=100, partitioned::Bool=false) where {T}
     h = tall_native(A, T)
-    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T) : C_NULL        # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain
-    h == C_NULL && c == C_NULL && error("hip_lsqr!: needs a tall block operator of device-native children, or a composite that is one fused FORWARD chain")
+    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T; grid=false) : C_NULL   # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain
+    h == C_NULL && c == C_NULL && error("hip_lsqr!: needs a tall block operator of device-native children, or a composite that is one fused FORWARD chain through a tall operator " *
+                                        "(through an N x K grid there is no one-pass step: use hip_cgnr!, or IterativeSolvers on the composite, whose mul! runs the fused grid chains)")
     res = Ref{jh_lsqr_result}()
     hist = Vector{Cdouble}(undef, 2 * maxiter)
     if c != C_NULL
@@ -1072,8 +1090,9 @@ end
 # overwritten (it becomes r = b - A x).  `partitioned=true`: the row-partitioned solve, a collective like hip_lsqr!'s
 function hip_cgls!(x::HipArray{T}, A::JopLn, b::BlockArray{T,<:HipArray{T}}; x0::Bool=false, damp=0.0, atol=1e-6, btol=1e-6, maxiter=100, partitioned::Bool=false) where {T}
     h = tall_native(A, T)
-    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T) : C_NULL        # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain
-    h == C_NULL && c == C_NULL && error("hip_cgls!: needs a tall block operator of device-native children, or a composite that is one fused FORWARD chain")
+    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T; grid=false) : C_NULL   # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain
+    h == C_NULL && c == C_NULL && error("hip_cgls!: needs a tall block operator of device-native children, or a composite that is one fused FORWARD chain through a tall operator " *
+                                        "(through an N x K grid there is no one-pass step: use hip_cgnr!, or IterativeSolvers on the composite, whose mul! runs the fused grid chains)")
     res = Ref{jh_lsqr_result}()
     hist = Vector{Cdouble}(undef, 2 * max(maxiter, 1))
     if c != C_NULL
@@ -1093,8 +1112,8 @@ end
 # CG on the normal equations through the fused A'A (one pass over the coefficients per iteration; b is only read)
 function hip_cgnr!(x::HipArray{T}, A::JopLn, b::BlockArray{T,<:HipArray{T}}; x0::Bool=false, damp=0.0, atol=1e-6, btol=1e-6, maxiter=100, partitioned::Bool=false) where {T}
     h = tall_native(A, T)
-    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T) : C_NULL        # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain
-    h == C_NULL && c == C_NULL && error("hip_cgnr!: needs a tall block operator of device-native children, or a composite that is one fused FORWARD chain")
+    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T) : C_NULL        # a weighted composite W ∘ A ∘ M (A tall or an N x (2 .. 4) grid): its FORWARD chain
+    h == C_NULL && c == C_NULL && error("hip_cgnr!: needs a tall block operator of device-native children, or a composite that is one fused FORWARD chain through a tall operator or an N x (2 .. 4) grid")
     res = Ref{jh_lsqr_result}()
     hist = Vector{Cdouble}(undef, 2 * max(maxiter, 1))
     if c != C_NULL
