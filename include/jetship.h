@@ -446,12 +446,19 @@ int jh_blockop_mul_adj_scaled(const jh_blockop *op, jh_bvec *m, const jh_bvec *d
  * i.e. jh_blockop_mul_axpby(op, u, v, alpha, beta, normsq) followed by jh_blockop_mul_adj(op, w, u), with u and w
  * bit-identical to that sequence, but every coefficient and every element of u is read once and u written once:
  * (3*N*n + 2*n)*s bytes instead of (5*N*n + 3*n)*s.  The solver then forms v <- w/||u|| - ||u||*v on domain-sized vectors
- * (A' is linear, so the normalisation of u can follow the pass).  Tall all-DIAG operators; w must not alias v. */
+ * (A' is linear, so the normalisation of u can follow the pass).  Tall all-DIAG operators; w must not alias v.
+ * GRID STEP: also an N x K grid (N >= 2, K = 2 .. 4) of equal elementwise blocks of >= 16 bytes -- diagonals, adjointed diagonals, zero, identity
+ * and scalar blocks, no nonlinear child --, vectors and coefficients aligned like their scalar (knob "grid_step" = 1, the default; 0: such grids
+ * return JH_ERR_UNSUPPORTED as before).  One pass keeps v_1 .. v_K and w_1 .. w_K in registers and walks the block rows in order: u_i is updated
+ * between the row's forward sum and its adjoint products, (N K + 2 N + 2 K) n s bytes.  u and w have the bits of jh_blockop_mul into a zeroed range
+ * vector, jh_lincomb(u, [alpha, beta], [t, u]) and jh_blockop_mul_adj (beta == 0: u = alpha t, u is not read); many rows of small blocks sum w in
+ * parts (knob adj_split = 0: the ordered walk).  Counter "last_grid_step_shape": bit 0 nontemporal loads, bit 1 rows in parts.  Other operators
+ * return JH_ERR_UNSUPPORTED before anything is touched. */
 int jh_blockop_bidiag_step(const jh_blockop *op, jh_bvec *u, const jh_bvec *v, jh_bvec *w, double alpha, double beta, double *normsq);
 /* The same step restricted to the elements [first_elem, first_elem+count) of the domain (16-byte aligned bounds): updates
  * those columns of every row of u, writes that range of w, and returns that range's share of ||u||^2 (the shares add up).
  * Lets a row-partitioned multi-GPU solver all-reduce chunk k of w while chunk k+1 is being computed.  Identical values
- * to jh_blockop_bidiag_step on those elements. */
+ * to jh_blockop_bidiag_step on those elements.  Tall operators only: a grid returns JH_ERR_UNSUPPORTED. */
 int jh_blockop_bidiag_step_range(const jh_blockop *op, jh_bvec *u, const jh_bvec *v, jh_bvec *w, double alpha, double beta,
                                  int64_t first_elem, int64_t count, double *normsq);
 /* Deferred ||u||^2 for a step enqueued range by range: with normsq == NULL jh_blockop_bidiag_step_range does not synchronise;
@@ -471,7 +478,9 @@ int jh_normsq_read(double *out);
  * (r1norm, arnorm) per iteration.  jh_lsqr_solve is always LOCAL to this process, whether or not a communicator exists.
  * jh_lsqr_solve_partitioned is the row-partitioned solve: `op`/`u` are this rank's block rows, x is replicated, and the
  * exchange (one all-reduce of the domain vector and one of a scalar per iteration) runs over the communicator of
- * jh_comm_init_rank; EVERY rank must call it, in lock-step (it is a collective).  With one rank it equals jh_lsqr_solve. */
+ * jh_comm_init_rank; EVERY rank must call it, in lock-step (it is a collective).  With one rank it equals jh_lsqr_solve.
+ * jh_lsqr_solve also takes an N x (2 .. 4) grid that jh_blockop_bidiag_step takes (GRID STEP above), host-driven on its one-pass step; the warm start
+ * u <- b - A x0 is one step into a scratch domain vector.  jh_lsqr_solve_partitioned and jh_lsqr_solve_team decline grids before touching anything. */
 typedef struct {
     int32_t istop, itn;
     double r1norm, r2norm, anorm, acond, arnorm, xnorm;
@@ -495,7 +504,9 @@ int jh_lsqr_solve_team(int n, const jh_blockop *const *ops, jh_bvec *const *us, 
  * return; `x` holds x0 when use_x0 != 0.  istop: 1 ||r|| <= btol ||b||; 2 ||A'r - damp^2 x|| <= atol times its starting value;
  * 6 breakdown (<p, (A'A + damp^2) p> not positive); 7 maxiter.  history (optional, 2*maxiter doubles): (||r||, ||A'r - damp^2 x||) per
  * iteration.  The result record is LSQR's (r1norm = ||r||, r2norm = sqrt(||r||^2 + damp^2 ||x||^2), arnorm, xnorm; anorm = acond = 0).
- * _partitioned / _team: the same exchange modes as the LSQR entry points (pass 1 exchanges ONE scalar; pass 2 is the pipelined step). */
+ * _partitioned / _team: the same exchange modes as the LSQR entry points (pass 1 exchanges ONE scalar; pass 2 is the pipelined step).
+ * jh_cgls_solve also takes an N x (2 .. 4) grid that both jh_blockop_bidiag_step (GRID STEP above) and jh_blockop_normal_mul take, host-driven;
+ * _partitioned and _team decline grids before touching anything. */
 int jh_cgls_solve(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int use_x0, double damp, double atol, double btol, int maxiter,
                   int force_maxiter, jh_lsqr_result *res, double *history);
 int jh_cgls_solve_partitioned(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int use_x0, double damp, double atol, double btol, int maxiter,
@@ -604,7 +615,7 @@ int jh_team_normal_mul(int n, const jh_blockop *const *ops, jh_bvec *const *ys, 
  * aligned loads of diagonals laid out like the range vector: -1 rows of 64 KiB or more, 0 never, 1 always; same bits), "tall_f" (F(m) of a tall nonlinear operator of elementwise children -- jh_blockop_f -- on the tall tiling: 1 yes, 0 the
  * general kernels; same bits), "dense_list_shared" (round 6: the rows pass of y = B x for DENSE children whose columns are off the 16-byte grid numbers its
  * chunks XCD by XCD and loads temporally, so the 128-byte line two neighbouring rows share is fetched from HBM once: 1 yes, 0 round 5's pass; same bits),
- * "dense_list_rl_min" (log2 of the fewest row lanes per workgroup of that pass, 0: automatic), "red_blocks_wave" (round 6: jh_norm_blocks / jh_dot_blocks of many blocks of at most 16 KiB with a wave per block in one launch: 1 yes, 0 a workgroup per block + the fold; within the reductions' tolerance of each other), "adj_bare_chain" (round 6: jh_blockop_mul_adj and jh_blockop_normal_mul of a tall operator with rows of several kinds, or rows off the 16-byte grid, of up to 4 MiB on the chain kernels with empty stage lists -- packed row records --: 1 yes, 0 the MIXED tall kernel; same bits unless the split walk's part count changes), "adj_thin_mixed" (round 6: the adjoint of a tall operator with rows of several kinds on thin workgroups when fat ones would leave CUs idle -- rows of 1-8 MiB --: 1 yes, 0 round 5's shapes; same bits unless the split walk's part count changes), "grid_normal" (round 6: jh_blockop_normal_mul on N x (2 .. 4) grids of equal elementwise blocks -- diagonals, zero / identity / scalar blocks -- in one pass: 1 yes, 2 grids of plain diagonals only, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_chain" (jh_chain_create on N x (2 .. 4) grids of equal elementwise blocks -- fused chains A' o W o A, (W o A)', W o A through a multi-parameter operator: 1 yes, 0 JH_ERR_UNSUPPORTED as before, the caller runs the composite stage by stage; same bits), "dense_combine" (round 6: operators whose non-zero blocks are
+ * "dense_list_rl_min" (log2 of the fewest row lanes per workgroup of that pass, 0: automatic), "red_blocks_wave" (round 6: jh_norm_blocks / jh_dot_blocks of many blocks of at most 16 KiB with a wave per block in one launch: 1 yes, 0 a workgroup per block + the fold; within the reductions' tolerance of each other), "adj_bare_chain" (round 6: jh_blockop_mul_adj and jh_blockop_normal_mul of a tall operator with rows of several kinds, or rows off the 16-byte grid, of up to 4 MiB on the chain kernels with empty stage lists -- packed row records --: 1 yes, 0 the MIXED tall kernel; same bits unless the split walk's part count changes), "adj_thin_mixed" (round 6: the adjoint of a tall operator with rows of several kinds on thin workgroups when fat ones would leave CUs idle -- rows of 1-8 MiB --: 1 yes, 0 round 5's shapes; same bits unless the split walk's part count changes), "grid_normal" (round 6: jh_blockop_normal_mul on N x (2 .. 4) grids of equal elementwise blocks -- diagonals, zero / identity / scalar blocks -- in one pass: 1 yes, 2 grids of plain diagonals only, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_step" (jh_blockop_bidiag_step, jh_lsqr_solve and jh_cgls_solve on N x (2 .. 4) grids of equal elementwise blocks in one pass per step: 1 yes, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_chain" (jh_chain_create on N x (2 .. 4) grids of equal elementwise blocks -- fused chains A' o W o A, (W o A)', W o A through a multi-parameter operator: 1 yes, 0 JH_ERR_UNSUPPORTED as before, the caller runs the composite stage by stage; same bits), "dense_combine" (round 6: operators whose non-zero blocks are
  * all DENSE children sum the products of a block line from CSR lists in one launch: 1 yes, 0 the general step lists; same bits);
  * round 4: "cg_dev" (jh_cgls_solve / jh_cgnr_solve with the recurrences on the device, graph-replayed unless lsqr_graph = 0: 1 automatic -- CGLS
  * like lsqr_graph, CG through the fused A'A up to 2 GiB of coefficients --, 2 at any size, 0 never: the host loops; within solver tolerance
@@ -627,7 +638,7 @@ int jh_team_normal_mul(int n, const jh_blockop *const *ops, jh_bvec *const *ys, 
  * "small_loop_max_kib" (operators of SMALL dense children whose matrices together reach this many KiB take
  * the list route instead of the one-launch loop: 512);
  * jh_tune_get also reads the counters "last_fwd_walk" (grid walk of the latest tall forward: 0 sequential, 1 all rows, 2 column bands),
- * "last_fwd_rows_per_wg", "last_adj_launches", "last_adj_parts", "last_grid_chain_shape" (how the latest grid chain was launched: see jh_chain_create), "last_step_chain" (row chunks of the latest one-pass step, 0: the plain walk), "graph_replays", "last_lsqr_graph" / "last_cg_graph" (graph replays of the latest
+ * "last_fwd_rows_per_wg", "last_adj_launches", "last_adj_parts", "last_grid_chain_shape" (how the latest grid chain was launched: see jh_chain_create), "last_grid_step_shape" (how the latest grid step was launched: see jh_blockop_bidiag_step), "last_step_chain" (row chunks of the latest one-pass step, 0: the plain walk), "graph_replays", "last_lsqr_graph" / "last_cg_graph" (graph replays of the latest
  * jh_lsqr_solve / jh_cgls_solve or jh_cgnr_solve; 0: the host loop ran) and "last_dense_fused" (1: the latest dense adjoint / wide forward took the
  * fused launch). */
 int jh_tune_set(const char *name, int64_t value);

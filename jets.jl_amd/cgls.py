@@ -20,7 +20,7 @@ import os
 from ._ffi import lib, check, JetsHipError
 from .arrays import reshape
 from . import jets as _j
-from .lsqr import LsqrResult, _Engine, _ShardEngine, _TeamEngine, _unwrap_vec, _chain_of, _count_chain_solve
+from .lsqr import LsqrResult, _Engine, _ShardEngine, _TeamEngine, _unwrap_vec, _chain_of, _count_chain_solve, _grid_of, _count_grid_solve
 
 __all__ = ["cgls", "cgls_core", "cgnr", "cgnr_core"]
 
@@ -61,7 +61,8 @@ def _native(eng, b, x0, damp, atol, btol, maxiter, overwrite_b, force_maxiter):
     from .rowpart import AbiComm
 
     chn = _chain_of(eng)
-    if os.environ.get("JETS_CGLS_NATIVE", "1") == "0" or (eng.native is None and chn is None):
+    grid = _grid_of(eng)
+    if os.environ.get("JETS_CGLS_NATIVE", "1") == "0" or (eng.native is None and chn is None and grid is None):
         return None
     shard = getattr(eng, "shard", None)
     if shard is not None and not (isinstance(shard.comm, AbiComm) or shard.comm.world == 1):
@@ -73,6 +74,8 @@ def _native(eng, b, x0, damp, atol, btol, maxiter, overwrite_b, force_maxiter):
     try:
         if chn is not None:                                     # one FORWARD chain: its NORMAL program and one-pass step (jh_cgls_solve_chain)
             solve, h = lib.jh_cgls_solve_chain, chn.fwd.handle
+        elif grid is not None:                                  # a bare grid: its fused A'A and one-pass step (jh_cgls_solve)
+            solve, h = lib.jh_cgls_solve, grid.handle
         else:
             solve, h = (lib.jh_cgls_solve_partitioned if shard is not None else lib.jh_cgls_solve), eng.native.handle
         check(solve(h, u.handle, x.handle, 0 if x0 is None else 1, float(damp), float(atol), float(btol), int(maxiter),
@@ -82,6 +85,7 @@ def _native(eng, b, x0, damp, atol, btol, maxiter, overwrite_b, force_maxiter):
             raise
         return None
     _count_chain_solve(chn)
+    _count_grid_solve(grid)
     return _result(x, res, hist)
 
 

@@ -34,7 +34,8 @@ ENABLED = [True]        # tests / A-B timings: [False] sends every composite and
 STATS = {"chain_calls": 0, "sum_terms_fused": 0, "bcast_calls": 0,    # how often a fused run was applied (tests assert that the fused path is the one that ran)
          "chain_range_calls": 0,                                      # ... and how often one ran on an element range of the domain (rowpart's pipelined exchange)
          "chain_step_calls": 0, "chain_solve_calls": 0,               # the solvers on a FORWARD chain: one-pass steps (jh_chain_bidiag_step), whole native solves (jh_*_solve_chain)
-         "grid_chain_calls": 0}                                       # fused runs through an N x (2 .. 4) grid (also counted in chain_calls / chain_solve_calls)
+         "grid_chain_calls": 0,                                       # fused runs through an N x (2 .. 4) grid (also counted in chain_calls / chain_solve_calls)
+         "grid_step_calls": 0, "grid_solve_calls": 0}                 # the solvers on a bare grid: one-pass steps (jh_blockop_bidiag_step), native LSQR / CGLS solves
 
 
 # ------------------------------------------------------------------------------ classification -----

@@ -15,36 +15,10 @@
 // blocks (skipped: 1022 / 1047), identities, scalars, adjointed diagonals -- through a packed table of one 64-bit word per block (pointer | kind << 48 |
 // adjoint << 51 | real scalar << 52, built on first use) and the lesson of the tall kernels: a batch of rows whose blocks are all PLAIN diagonals takes the tight
 // loop, any other batch the per-block switch.
-#include "jh_blockop_common.h"
+#include "jh_grid_common.h"
 #include <vector>
 
 namespace {
-
-constexpr uint64_t GW_PTR = (((uint64_t)1) << 48) - 1;
-__device__ inline int gw_kind(uint64_t w) { return (int)((w >> 48) & 7u); }
-__device__ inline bool gw_adj(uint64_t w) { return ((w >> 51) & 1u) != 0; }
-__device__ inline bool gw_real(uint64_t w) { return ((w >> 52) & 1u) != 0; }
-
-// child mul! of block `idx` on a pack (jh_blockop_common.h: apply_block_loaded, on the block's table word; scalars from the block table)
-template <typename S, int E, int NS, typename V>
-__device__ inline V grid_apply(uint64_t w, const jh_dev_block *blocks, int64_t idx, V x, V c, bool transposed)
-{
-    const bool cj = gw_adj(w) != transposed;
-    switch (gw_kind(w)) {
-    case JH_OP_DIAG: return vmul<S, E, NS, V>(c, x, cj);
-    case JH_OP_IDENTITY: return x;
-    case JH_OP_SCALE: {
-        const double sre = blocks[idx].sre;
-        if (E == 1 || gw_real(w)) return (V)(S)sre * x;
-        const double sim = blocks[idx].sim;
-        V a;
-#pragma unroll
-        for (int q = 0; q < NS; q += 2) { a[q] = (S)sre; a[q + 1] = (S)sim; }
-        return vmul<S, E, NS, V>(a, x, cj);
-    }
-    default: return (V)(S)0;
-    }
-}
 
 // the same walk over the PACKED table (MIXED grids): words[(i) * K + k]
 template <typename S, int E, int NS, int K, int DEPTH, bool NT>
@@ -254,47 +228,59 @@ int grid_normal_k(const jh_blockop *op, void *y, const void *m)
 
 namespace jhb {
 
-// an N x K grid (N >= 2, K = 2 .. 4) of equal blocks -- plain diagonals, or (knob grid_normal = 1: later in round 6) zero / identity / scalar / diagonal blocks, no
-// nonlinear child --, vectors and coefficients aligned like their scalar
-bool grid_normal_ok(const jh_blockop *op, const void *y, const void *m)
+// an N x K grid (N >= 2, K = 2 .. 4) of equal blocks of >= 16 bytes -- plain diagonals, or (mixed_ok) zero / identity / scalar / diagonal blocks, no
+// nonlinear child --, coefficients aligned like their scalar
+bool grid_shape_ok(const jh_blockop *op, bool mixed_ok)
 {
-    const int64_t knob = jh_ctx().grid_normal;
-    if (!(op->nrow >= 2 && op->ncol >= 2 && op->ncol <= 4 && op->uniform_rows) || knob == 0) return false;
+    if (!(op->nrow >= 2 && op->ncol >= 2 && op->ncol <= 4 && op->uniform_rows)) return false;
     if (!op->all_diag) {
-        if (knob == 2 || !op->elementwise || op->nonlinear || op->wide_scale) return false;
+        if (!mixed_ok || !op->elementwise || op->nonlinear || op->wide_scale) return false;
         for (const jh_block_desc &b : op->blocks)
             if (b.kind != JH_OP_ZERO && b.kind != JH_OP_IDENTITY && b.kind != JH_OP_SCALE && b.kind != JH_OP_DIAG) return false;
     }
-    const size_t es = jh_dtype_size(op->dtype), sa = jh_dtype_complex(op->dtype) ? es / 2 : es;
+    const size_t es = jh_dtype_size(op->dtype);
     const int64_t n = op->row_len[0];
     if (n * (int64_t)es < 16) return false;
     for (int64_t v : op->col_len)
         if (v != n) return false;
-    if ((((uintptr_t)y) | ((uintptr_t)m)) & (sa - 1)) return false;
     return op->coeff_scalar_aligned;
+}
+
+// the grids above (knob grid_normal = 1: later in round 6, grids of several kinds), vectors aligned like their scalar
+bool grid_normal_ok(const jh_blockop *op, const void *y, const void *m)
+{
+    const int64_t knob = jh_ctx().grid_normal;
+    if (knob == 0 || !grid_shape_ok(op, knob != 2)) return false;
+    const size_t es = jh_dtype_size(op->dtype), sa = jh_dtype_complex(op->dtype) ? es / 2 : es;
+    return ((((uintptr_t)y) | ((uintptr_t)m)) & (sa - 1)) == 0;
+}
+
+int grid_words_ensure(const jh_blockop *op)
+{
+    if (op->all_diag || op->grid_words) return JH_OK;
+    if (stream_is_capturing(jh_ctx().stream))                 // (an allocation and a synchronous copy: not inside a stream capture -- the caller chains the two stages)
+        return jh_fail(JH_ERR_UNSUPPORTED, "grid kernels: the block table of this operator is built on the first call, which must not be inside a stream capture");
+    const size_t nw = (size_t)op->nrow * (size_t)op->ncol;
+    std::vector<uint64_t> h(nw);
+    for (int64_t i = 0; i < op->nrow; i++)
+        for (int64_t k = 0; k < op->ncol; k++) {
+            const jh_block_desc &b = op->blocks[(size_t)(i + k * op->nrow)];
+            const jh_dev_block db = jh_dev_block_of(b);
+            const uint64_t p = (uint64_t)(uintptr_t)(b.kind == JH_OP_DIAG ? b.coeff : nullptr);
+            JH_REQUIRE((p >> 48) == 0, "grid kernels: a coefficient address does not fit 48 bits");
+            h[(size_t)(i * op->ncol + k)] = p | ((uint64_t)(b.kind & 7) << 48) | ((uint64_t)(b.adjoint ? 1 : 0) << 51) | ((uint64_t)(db.real_scale ? 1 : 0) << 52);
+        }
+    void *dev = nullptr;
+    JH_CHECK_HIP(hipMalloc(&dev, nw * sizeof(uint64_t)));
+    const hipError_t e = hipMemcpy(dev, h.data(), nw * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(dev); JH_CHECK_HIP(e); }
+    op->grid_words = dev;
+    return JH_OK;
 }
 
 int grid_normal(const jh_blockop *op, void *y, const void *m)
 {
-    if (!op->all_diag && !op->grid_words) {                   // the packed table of a mixed grid, row-major (N x K words), built on first use
-        if (stream_is_capturing(jh_ctx().stream))             // (an allocation and a synchronous copy: not inside a stream capture -- the caller chains the two stages)
-            return jh_fail(JH_ERR_UNSUPPORTED, "grid normal: the block table of this operator is built on the first call, which must not be inside a stream capture");
-        const size_t nw = (size_t)op->nrow * (size_t)op->ncol;
-        std::vector<uint64_t> h(nw);
-        for (int64_t i = 0; i < op->nrow; i++)
-            for (int64_t k = 0; k < op->ncol; k++) {
-                const jh_block_desc &b = op->blocks[(size_t)(i + k * op->nrow)];
-                const jh_dev_block db = jh_dev_block_of(b);
-                const uint64_t p = (uint64_t)(uintptr_t)(b.kind == JH_OP_DIAG ? b.coeff : nullptr);
-                JH_REQUIRE((p >> 48) == 0, "grid normal: a coefficient address does not fit 48 bits");
-                h[(size_t)(i * op->ncol + k)] = p | ((uint64_t)(b.kind & 7) << 48) | ((uint64_t)(b.adjoint ? 1 : 0) << 51) | ((uint64_t)(db.real_scale ? 1 : 0) << 52);
-            }
-        void *dev = nullptr;
-        JH_CHECK_HIP(hipMalloc(&dev, nw * sizeof(uint64_t)));
-        const hipError_t e = hipMemcpy(dev, h.data(), nw * sizeof(uint64_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(dev); JH_CHECK_HIP(e); }
-        op->grid_words = dev;
-    }
+    JH_TRY(grid_words_ensure(op));                            // the packed table of a mixed grid, row-major (N x K words), built on first use
     switch (op->dtype) {
     case JH_F32: return grid_normal_k<float, 1, 4>(op, y, m);
     case JH_F64: return grid_normal_k<double, 1, 2>(op, y, m);

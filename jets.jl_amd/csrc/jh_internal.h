@@ -143,6 +143,8 @@ struct jh_context {
     int64_t grid_normal = 1;           // knob: (A', A) on an N x (2 .. 4) grid of equal elementwise blocks in one pass (jh_grid_normal.hip); 2: grids of plain diagonals only; 0: JH_ERR_UNSUPPORTED as in rounds 1-5 (the caller chains the two stages)
     int64_t grid_chain = 1;            // knob: jh_chain_create on an N x (2 .. 4) grid of equal elementwise blocks (jh_grid_chain.hip): 1 yes, 0 JH_ERR_UNSUPPORTED as before (the caller runs the chain stage by stage)
     int64_t last_grid_chain_shape = 0; // how the most recent grid chain was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts, bit 2 the stages after A' on the folded parts
+    int64_t grid_step = 1;             // knob: jh_blockop_bidiag_step (and the LSQR / CGLS loops of jh_lsqr_solve / jh_cgls_solve) on an N x (2 .. 4) grid of equal elementwise blocks in one pass (jh_grid_step.hip): 1 yes, 0 JH_ERR_UNSUPPORTED as before
+    int64_t last_grid_step_shape = 0;  // how the most recent grid step was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
     int64_t fwd_anchor = -1;           // knob: the tall forward of rows that are not whole packs on lanes anchored to each row's own 16-byte grid (k_tall_fwd_anchored): -1 from 64 KiB rows on, 0 never, 1 always
     int64_t wide_twin = 1;             // knob: wide elementwise operators on their tall twin: 0 never (general kernels), 1 adjoint always + forward from 16 MiB blocks, 2 both always (tests)
     const double *step_coef_dev = nullptr;   // internal, set around the calls of the graph-captured LSQR loop: the one-pass step reads (alpha, beta) from
@@ -167,6 +169,10 @@ jh_context &jh_ctx();                  // the calling thread's current context (
 // wrong for an operator that fits -- its coefficients would come from HBM every iteration although the cache could hold them.
 // Knob nt: 0 never, 2 always, 1 (default): nontemporal unless the working set of one pass is at most nt_resident_mib.
 namespace jhb { bool grid_normal_ok(const jh_blockop *op, const void *y, const void *m); }   // jh_grid_normal.hip
+namespace jhb {   // jh_grid_step.hip: the one-pass Golub-Kahan step of an N x (2 .. 4) grid of equal elementwise blocks (knob grid_step; vectors aligned like their scalar)
+bool grid_step_ok(const jh_blockop *op, const void *u, const void *v, const void *w);
+int grid_step(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq);
+}
 namespace jhb {   // jh_tall_chain.hip: L' (JH_CHAIN_ADJOINT) / L'L (JH_CHAIN_NORMAL) of a FORWARD chain; the checks of the solvers on a chain (op: its operator)
 int chain_apply_derived(const jh_chain *fwd, int which, jh_bvec *out, const jh_bvec *in);
 int chain_solver_ok(const jh_chain *fwd, const jh_bvec *u, const jh_bvec *x, const jh_blockop **op, bool needs_step = true);   // needs_step: the loop takes jh_chain_bidiag_step (LSQR, CGLS; a grid chain has none)

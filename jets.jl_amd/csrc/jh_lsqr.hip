@@ -340,10 +340,12 @@ enum class Exch { none, ranks, team };
 
 // The four passes the loops below take from a shard: a block operator's fused kernels, or (one GPU, jh_*_solve_chain) a FORWARD chain L = R o A o P
 // and the programs derived from it.  A chain has no forward-with-axpby of its own: the warm start u <- b - L x0 is one step into a scratch domain vector.
+// An N x (2 .. 4) grid (one GPU, jh_lsqr_solve / jh_cgls_solve) has no forward-with-axpby either: its warm start is the same scratch step (jh_grid_step.hip).
 struct Passes {
     const jh_blockop *op = nullptr;
     const jh_chain *ch = nullptr;
-    jh_bvec *scratch = nullptr;                  // (chain: the step's w of the warm start)
+    bool grid = false;                           // op is a grid (jhb::grid_step_ok)
+    jh_bvec *scratch = nullptr;                  // (chain, grid: the step's w of the warm start)
     Passes() = default;
     Passes(const Passes &) = delete;
     Passes &operator=(const Passes &) = delete;
@@ -351,12 +353,12 @@ struct Passes {
     // u <- a*(L x) + b*u, ||u||^2
     int fwd_axpby(jh_bvec *u, const jh_bvec *x, double a, double b, double *normsq)
     {
-        if (!ch) return jh_blockop_mul_axpby(op, u, x, a, b, normsq);
+        if (!ch && !grid) return jh_blockop_mul_axpby(op, u, x, a, b, normsq);
         if (!scratch) {
             const int64_t len1[1] = {x->length};
             JH_TRY(jh_bvec_create(1, len1, x->dtype, &scratch));
         }
-        return jh_chain_bidiag_step(ch, u, x, scratch, a, b, normsq);
+        return ch ? jh_chain_bidiag_step(ch, u, x, scratch, a, b, normsq) : jh_blockop_bidiag_step(op, u, x, scratch, a, b, normsq);
     }
     // out = L' in
     int adjoint(jh_bvec *out, const jh_bvec *in) { return ch ? jhb::chain_apply_derived(ch, JH_CHAIN_ADJOINT, out, in) : jh_blockop_mul_adj(op, out, in); }
@@ -371,7 +373,7 @@ struct Passes {
 
 static int lsqr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *us, jh_bvec *const *xs, int use_x0, double damp, double atol,
                      double btol, double conlim, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history, const Exch ex,
-                     const jh_chain *ch = nullptr)
+                     const jh_chain *ch = nullptr, const bool grid_ok = false)
 {
     JH_REQUIRE(ops && us && xs && res && M >= 1, "jh_lsqr_solve: null argument");
     JH_REQUIRE(maxiter >= 0, "jh_lsqr_solve: maxiter must be >= 0");
@@ -385,11 +387,14 @@ static int lsqr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
         JH_REQUIRE(xs[k]->length == n && xs[k]->dtype == dtype, "jh_lsqr_solve: member %d's x differs in length or element type", k);
         // before anything is touched: the caller can still take another path.  Rows off the 16-byte pack grid are fine (jh_blockop_tall_step_ok): the
         // pipelined exchange cuts the DOMAIN at 16-byte bounds, and the last range may end with the vector
-        if (!ch && !jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data))
+        // grid_ok (jh_lsqr_solve: one GPU, unpartitioned): an N x (2 .. 4) grid of equal elementwise blocks on its one-pass step (jh_grid_step.hip)
+        const bool grid = grid_ok && !ch && M == 1 && ex == Exch::none && !jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data) &&
+                          jhb::grid_step_ok(ops[k], us[k]->data, xs[k]->data, xs[k]->data);
+        if (!ch && !grid && !jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data))
             return jh_fail(JH_ERR_UNSUPPORTED, "jh_lsqr_solve: needs a tall operator of >= 2 equal elementwise rows");
     }
     std::vector<Passes> pass((size_t)M);
-    for (int k = 0; k < M; k++) { pass[k].op = ops[k]; pass[k].ch = ch; }
+    for (int k = 0; k < M; k++) { pass[k].op = ops[k]; pass[k].ch = ch; pass[k].grid = !ch && !jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data); }
     std::vector<Tmp> t((size_t)M);
     const int64_t len1[1] = {n};
     const int64_t ns_dom = n * (jh_dtype_complex(dtype) ? 2 : 1);
@@ -785,7 +790,7 @@ extern "C" int jh_lsqr_solve(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int u
     bool took = false;
     JH_TRY(lsqr_graph_impl(op, u, x, use_x0, damp, atol, btol, conlim, maxiter, force_maxiter, res, history, &took));   // small operators
     if (took) return JH_OK;
-    return lsqr_impl(1, &op, &u, &x, use_x0, damp, atol, btol, conlim, maxiter, force_maxiter, res, history, Exch::none);
+    return lsqr_impl(1, &op, &u, &x, use_x0, damp, atol, btol, conlim, maxiter, force_maxiter, res, history, Exch::none, nullptr, true);
 }
 
 extern "C" int jh_lsqr_solve_partitioned(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int use_x0, double damp, double atol, double btol,
@@ -842,7 +847,7 @@ extern "C" int jh_lsqr_solve_team(int n, const jh_blockop *const *ops, jh_bvec *
 // <p, A_k'A_k p>), the second is LSQR's pipelined step (ranged all-reduces of A'r under the kernels, one host synchronisation).
 static int cgls_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *us, jh_bvec *const *xs, int use_x0, double damp, double atol,
                      double btol, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history, const Exch ex,
-                     const jh_chain *ch = nullptr)
+                     const jh_chain *ch = nullptr, const bool grid_ok = false)
 {
     JH_REQUIRE(ops && us && xs && res && M >= 1, "jh_cgls_solve: null argument");
     JH_REQUIRE(maxiter >= 0, "jh_cgls_solve: maxiter must be >= 0");
@@ -855,11 +860,15 @@ static int cgls_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
     for (int k = 0; k < M; k++) {
         JH_REQUIRE(xs[k]->length == n && xs[k]->dtype == dtype, "jh_cgls_solve: member %d's x differs in length or element type", k);
         // before anything is touched (rows off the 16-byte pack grid too, as in lsqr_impl)
-        if (!ch && (!jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data) || ops[k]->nrow < 2))
+        // grid_ok (jh_cgls_solve: one GPU, unpartitioned): an N x (2 .. 4) grid of equal elementwise blocks -- its one-pass step (jh_grid_step.hip) and its
+        // fused A'A (jh_grid_normal.hip) are both checked here
+        const bool grid = grid_ok && !ch && M == 1 && ex == Exch::none && !jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data) &&
+                          jhb::grid_step_ok(ops[k], us[k]->data, xs[k]->data, xs[k]->data) && jhb::grid_normal_ok(ops[k], xs[k]->data, xs[k]->data);
+        if (!ch && !grid && (!jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data) || ops[k]->nrow < 2))
             return jh_fail(JH_ERR_UNSUPPORTED, "jh_cgls_solve: needs a tall (>= 2 rows) operator of equal elementwise rows");
     }
     std::vector<Passes> pass((size_t)M);
-    for (int k = 0; k < M; k++) { pass[k].op = ops[k]; pass[k].ch = ch; }
+    for (int k = 0; k < M; k++) { pass[k].op = ops[k]; pass[k].ch = ch; pass[k].grid = !ch && !jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data); }
     struct Work {                                                         // domain-sized work vectors of one member
         jh_bvec *p = nullptr, *s = nullptr, *y = nullptr;
         ~Work()
@@ -1375,7 +1384,7 @@ extern "C" int jh_cgls_solve(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int u
     bool took = false;
     JH_TRY(cg_dev_impl(op, u, x, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history, true, &took));   // small operators: recurrences on the device
     if (took) return JH_OK;
-    return cgls_impl(1, &op, &u, &x, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history, Exch::none);
+    return cgls_impl(1, &op, &u, &x, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history, Exch::none, nullptr, true);
 }
 
 extern "C" int jh_cgls_solve_partitioned(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int use_x0, double damp, double atol, double btol,

@@ -1035,8 +1035,11 @@ int jh_blockop_bidiag_step(const jh_blockop *op, jh_bvec *u, const jh_bvec *v, j
     JH_REQUIRE(w && w->dtype == op->dtype && w->length == v->length, "jh_blockop_bidiag_step: w must be a domain vector of the operator");
     JH_REQUIRE(w->data != v->data, "jh_blockop_bidiag_step: w must not alias v");
     // (round 5, session 3: rows off the 16-byte pack grid -- odd block lengths in one slab -- run the plain walk's MIXED instantiations on under-aligned packs)
-    if (!jh_blockop_tall_step_ok(op, u->data, v->data) || (((uintptr_t)w->data) & (jh_dtype_size(op->dtype) / (jh_dtype_complex(op->dtype) ? 2 : 1) - 1)))
-        return jh_fail(JH_ERR_UNSUPPORTED, "jh_blockop_bidiag_step: needs a tall operator of >= 2 equal elementwise rows");
+    if (!jh_blockop_tall_step_ok(op, u->data, v->data) || (((uintptr_t)w->data) & (jh_dtype_size(op->dtype) / (jh_dtype_complex(op->dtype) ? 2 : 1) - 1))) {
+        // an N x (2 .. 4) grid of equal elementwise blocks: the grid's own one-pass kernel (jh_grid_step.hip; knob grid_step)
+        if (jhb::grid_step_ok(op, u->data, v->data, w->data)) return jhb::grid_step(op, u->data, v->data, w->data, alpha, beta, normsq);
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_blockop_bidiag_step: needs a tall operator of >= 2 equal elementwise rows or an N x (2 .. 4) grid of equal elementwise blocks");
+    }
     const int64_t n = op->row_len[0];
     switch (op->dtype) {
     case JH_F32: return launch_bidiag<float, 1, 4>(op, u->data, v->data, w->data, n, alpha, beta, normsq);

@@ -77,6 +77,11 @@ class _Engine:
         # the row-partitioned and team engines keep their routes.
         self.chains = None
         self._tmp_q = None
+        # a bare N x (2 .. 4) grid (one GPU): its own one-pass step and the native LSQR / CGLS loops on it (jh_grid_step.hip); None when the operator is
+        # no grid, or once the library has declined the step
+        self.grid = None
+        if self.native is None and type(self) is _Engine and isinstance(A, _j.JopLn):
+            self.grid = _blk._grid_native(A)
         if self.native is None and type(self) is _Engine:
             from . import chains as _chn
 
@@ -162,8 +167,29 @@ class _Engine:
             nrm2 = self.chains.step(u, v, self._tmp_d, alpha, beta)
             if nrm2 is not None:
                 return math.sqrt(nrm2), self._tmp_d
+        if self.grid is not None and self.fused_step:
+            nrm2 = self._grid_step(u, v, alpha, beta)
+            if nrm2 is not None:
+                return math.sqrt(nrm2), self._tmp_d
         r = self._step_local(u, v, alpha, beta)
         return None if r is None else (math.sqrt(r[0]), r[1])
+
+    def _grid_step(self, u, v, alpha, beta):
+        """The grid's one-pass step into self._tmp_d; ||u||^2, or None when the library declines (the grid is then dropped: two halves from here on)."""
+        from . import chains as _chn
+
+        if self._tmp_d is None:
+            self._tmp_d = zeros(_j.domain(self.A))
+        out = C.c_double(0)
+        try:
+            check(lib.jh_blockop_bidiag_step(self.grid.handle, u.handle, v.handle, self._tmp_d.handle, float(alpha), float(beta), C.byref(out)))
+        except JetsHipError as e:
+            if e.status != 4:                                   # JH_ERR_UNSUPPORTED comes before anything is touched
+                raise
+            self.grid = None
+            return None
+        _chn.STATS["grid_step_calls"] += 1
+        return out.value
 
     def _chain_normal(self, y, p) -> float:
         """y = L'L p as ONE NORMAL chain (cgnr_core's hook); returns <p, y>.  Should the library decline the handle, A then A' through a range
@@ -337,7 +363,8 @@ def _native_solve(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, fo
     from .rowpart import AbiComm
 
     chn = _chain_of(eng)
-    if os.environ.get("JETS_LSQR_NATIVE", "1") == "0" or (eng.native is None and chn is None) or not eng.fused_step:
+    grid = _grid_of(eng)
+    if os.environ.get("JETS_LSQR_NATIVE", "1") == "0" or (eng.native is None and chn is None and grid is None) or not eng.fused_step:
         return None
     shard = getattr(eng, "shard", None)
     if shard is not None and not (isinstance(shard.comm, AbiComm) or shard.comm.world == 1):
@@ -350,6 +377,8 @@ def _native_solve(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, fo
         # a rank-local operator is solved locally even while an AbiComm is alive; only a RowPartitionedOp is a collective solve
         if chn is not None:                                     # one FORWARD chain: jh_lsqr_solve_chain iterates on its one-pass step
             solve, h = lib.jh_lsqr_solve_chain, chn.fwd.handle
+        elif grid is not None:                                  # a bare grid: jh_lsqr_solve iterates on the grid's one-pass step
+            solve, h = lib.jh_lsqr_solve, grid.handle
         else:
             solve, h = (lib.jh_lsqr_solve_partitioned if shard is not None else lib.jh_lsqr_solve), eng.native.handle
         check(solve(h, u.handle, x.handle, 0 if x0 is None else 1, float(damp), float(atol), float(btol),
@@ -359,8 +388,22 @@ def _native_solve(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, fo
             raise
         return None
     _count_chain_solve(chn)
+    _count_grid_solve(grid)
     history = [(k + 1, hist[2 * k], hist[2 * k + 1]) for k in builtins.range(res.itn)]
     return LsqrResult(x, res.istop, res.itn, res.r1norm, res.r2norm, res.anorm, res.acond, res.arnorm, res.xnorm, history)
+
+
+def _grid_of(eng):
+    """The one-GPU engine's bare grid (the NativeBlockOp of an N x (2 .. 4) block operator) when the native solve runs on it, else None."""
+    grid = getattr(eng, "grid", None)
+    return grid if grid is not None and eng.native is None and _chain_of(eng) is None and getattr(eng, "shard", None) is None else None
+
+
+def _count_grid_solve(grid):
+    if grid is not None:
+        from . import chains as _chn
+
+        _chn.STATS["grid_solve_calls"] += 1
 
 
 def _chain_of(eng):

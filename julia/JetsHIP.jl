@@ -1027,8 +1027,10 @@ function mul_adj_scaled!(m::HipArray{T}, a::Real, A::JopLn, d::BlockArray{T,<:Hi
 end
 
 # one whole Golub-Kahan step in one pass: u <- alpha*(A v) + beta*u ; w <- A'u ; returns ||u||   (3/5 of the bytes of the two halves)
+# A tall operator, or a bare N x (2 .. 4) grid of equal elementwise blocks (jh_grid_step.hip: the library declines the grids it has no kernel for)
 function bidiag_step!(u::BlockArray{T,<:HipArray{T}}, w::HipArray{T}, A::JopLn, v::HipArray{T}, alpha::Real, beta::Real) where {T}
     h = tall_native(A, T)
+    h == C_NULL && (h = grid_native(A, T))
     h == C_NULL && return bidiag_step!(u, w, _plan_chain(A, T; grid=false), v, alpha, beta)   # (a grid chain has no one-pass step)
     nrm2 = Ref{Cdouble}()
     check(ccall((:jh_blockop_bidiag_step, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ref{Cdouble}),
@@ -1038,7 +1040,8 @@ end
 # the same step over a FORWARD chain L = R ∘ A ∘ P (a weighted operator W ∘ A, W ∘ A ∘ M, a * (W ∘ A): the composite 530-540 in the solvers' loop
 # 1138-1154): u <- alpha*(L v) + beta*u ; w <- L'u ; ||u|| in ONE pass over A, the weights and u (jh_chain_bidiag_step)
 function bidiag_step!(u::BlockArray{T,<:HipArray{T}}, w::HipArray{T}, chain::Ptr{Cvoid}, v::HipArray{T}, alpha::Real, beta::Real) where {T}
-    chain == C_NULL && error("bidiag_step!: needs a tall block operator or a composite that is one fused FORWARD chain through a tall operator (N x K grids have no one-pass step)")
+    chain == C_NULL && error("bidiag_step!: needs a tall block operator, an N x (2 .. 4) block operator, or a composite that is one fused FORWARD chain through a tall operator " *
+                             "(a weighted N x K grid has no one-pass step)")
     nrm2 = Ref{Cdouble}()
     check(ccall((:jh_chain_bidiag_step, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ref{Cdouble}),
                 chain, handle(u), handle(v), handle(w), alpha, beta, nrm2))
@@ -1066,9 +1069,10 @@ end
 struct jh_lsqr_result; istop::Int32; itn::Int32; r1norm::Cdouble; r2norm::Cdouble; anorm::Cdouble; acond::Cdouble; arnorm::Cdouble; xnorm::Cdouble; end
 function hip_lsqr!(x::HipArray{T}, A::JopLn, b::BlockArray{T,<:HipArray{T}}; x0::Bool=false, damp=0.0, atol=1e-6, btol=1e-6, conlim=1e8, maxiter=100, partitioned::Bool=false) where {T}
     h = tall_native(A, T)
+    (h == C_NULL && !partitioned) && (h = grid_native(A, T))                  # a bare N x (2 .. 4) grid: the loop on its one-pass step (one GPU; the library declines the kinds it has no kernel for)
     c = (h == C_NULL && !partitioned) ? _plan_chain(A, T; grid=false) : C_NULL   # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain
-    h == C_NULL && c == C_NULL && error("hip_lsqr!: needs a tall block operator of device-native children, or a composite that is one fused FORWARD chain through a tall operator " *
-                                        "(through an N x K grid there is no one-pass step: use hip_cgnr!, or IterativeSolvers on the composite, whose mul! runs the fused grid chains)")
+    h == C_NULL && c == C_NULL && error("hip_lsqr!: needs a tall block operator of device-native children, an N x (2 .. 4) block operator (one GPU), or a composite that is one fused FORWARD chain " *
+                                        "through a tall operator (a weighted N x K grid has no one-pass step: use hip_cgnr!, or IterativeSolvers on the composite, whose mul! runs the fused grid chains)")
     res = Ref{jh_lsqr_result}()
     hist = Vector{Cdouble}(undef, 2 * maxiter)
     if c != C_NULL
@@ -1090,9 +1094,10 @@ end
 # overwritten (it becomes r = b - A x).  `partitioned=true`: the row-partitioned solve, a collective like hip_lsqr!'s
 function hip_cgls!(x::HipArray{T}, A::JopLn, b::BlockArray{T,<:HipArray{T}}; x0::Bool=false, damp=0.0, atol=1e-6, btol=1e-6, maxiter=100, partitioned::Bool=false) where {T}
     h = tall_native(A, T)
+    (h == C_NULL && !partitioned) && (h = grid_native(A, T))                  # a bare N x (2 .. 4) grid: the loop on its one-pass step (one GPU; the library declines the kinds it has no kernel for)
     c = (h == C_NULL && !partitioned) ? _plan_chain(A, T; grid=false) : C_NULL   # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain
-    h == C_NULL && c == C_NULL && error("hip_cgls!: needs a tall block operator of device-native children, or a composite that is one fused FORWARD chain through a tall operator " *
-                                        "(through an N x K grid there is no one-pass step: use hip_cgnr!, or IterativeSolvers on the composite, whose mul! runs the fused grid chains)")
+    h == C_NULL && c == C_NULL && error("hip_cgls!: needs a tall block operator of device-native children, an N x (2 .. 4) block operator (one GPU), or a composite that is one fused FORWARD chain " *
+                                        "through a tall operator (a weighted N x K grid has no one-pass step: use hip_cgnr!, or IterativeSolvers on the composite, whose mul! runs the fused grid chains)")
     res = Ref{jh_lsqr_result}()
     hist = Vector{Cdouble}(undef, 2 * max(maxiter, 1))
     if c != C_NULL
