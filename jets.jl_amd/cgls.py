@@ -13,14 +13,9 @@ textbook loop (q = A p kept in a range vector) over the same engines as LSQR: th
 from __future__ import annotations
 
 import builtins
-import ctypes as C
 import math
-import os
 
-from ._ffi import lib, check, JetsHipError
-from .arrays import reshape
-from . import jets as _j
-from .lsqr import LsqrResult, _Engine, _ShardEngine, _TeamEngine, _unwrap_vec, _chain_of, _count_chain_solve, _grid_of, _count_grid_solve
+from .lsqr import LsqrResult, _engine_for, _native_solve
 
 __all__ = ["cgls", "cgls_core", "cgnr", "cgnr_core"]
 
@@ -31,85 +26,9 @@ def cgls(A, b, x0=None, damp: float = 0.0, atol: float = 1e-6, btol: float = 1e-
     rank's rows, every rank gets the same x) or a rowpart.TeamOp (b, x: TeamVec).  istop: 1 ||r|| <= btol ||b||, 2 ||A'r - damp^2 x||
     <= atol times its starting value, 6 breakdown, 7 maxiter.  The record is LSQR's (r1norm = ||r||, arnorm = ||A'r - damp^2 x||,
     history = (itn, ||r||, ||A'r - damp^2 x||) per iteration; anorm = acond = 0).  `overwrite_b=True`: b's storage becomes r."""
-    from .rowpart import RowPartitionedOp, TeamOp
-
-    if isinstance(A, TeamOp):
-        eng = _TeamEngine(A)
-        native = _native_team(eng, b, x0, damp, atol, btol, maxiter, overwrite_b, force_maxiter)
-        return native if native is not None else cgls_core(eng, b, x0, damp, atol, btol, maxiter, overwrite_b, force_maxiter)
-    if isinstance(A, RowPartitionedOp):
-        eng = _ShardEngine(A)
-        dom, rng = _j.domain(A.local_op), _j.range_(A.local_op)
-    else:
-        A = _unwrap_vec(A)
-        eng = _Engine(A)
-        dom, rng = _j.domain(A), _j.range_(A)
-    b = reshape(b, rng)
-    x0 = None if x0 is None else reshape(x0, dom)
-    native = _native(eng, b, x0, damp, atol, btol, maxiter, overwrite_b, force_maxiter)
-    return native if native is not None else cgls_core(eng, b, x0, damp, atol, btol, maxiter, overwrite_b, force_maxiter)
-
-
-def _result(x, res, hist):
-    history = [(k + 1, hist[2 * k], hist[2 * k + 1]) for k in builtins.range(res.itn)]
-    return LsqrResult(x, res.istop, res.itn, res.r1norm, res.r2norm, res.anorm, res.acond, res.arnorm, res.xnorm, history)
-
-
-def _native(eng, b, x0, damp, atol, btol, maxiter, overwrite_b, force_maxiter):
-    """jh_cgls_solve (one GPU) / jh_cgls_solve_partitioned (the ABI's own RCCL communicator).  None when it does not apply."""
-    from ._ffi import LsqrResultC
-    from .rowpart import AbiComm
-
-    chn = _chain_of(eng)
-    grid = _grid_of(eng)
-    if os.environ.get("JETS_CGLS_NATIVE", "1") == "0" or (eng.native is None and chn is None and grid is None):
-        return None
-    shard = getattr(eng, "shard", None)
-    if shard is not None and not (isinstance(shard.comm, AbiComm) or shard.comm.world == 1):
-        return None
-    x = eng.zeros_dom() if x0 is None else eng.copy(eng.zeros_dom(), x0)
-    u = b if overwrite_b else (eng.copy_of_rng(b) if hasattr(eng, "copy_of_rng") else eng.copy(eng.zeros_rng(), b))
-    res = LsqrResultC()
-    hist = (C.c_double * builtins.max(2 * int(maxiter), 1))()
-    try:
-        if chn is not None:                                     # one FORWARD chain: its NORMAL program and one-pass step (jh_cgls_solve_chain)
-            solve, h = lib.jh_cgls_solve_chain, chn.fwd.handle
-        elif grid is not None:                                  # a bare grid: its fused A'A and one-pass step (jh_cgls_solve)
-            solve, h = lib.jh_cgls_solve, grid.handle
-        else:
-            solve, h = (lib.jh_cgls_solve_partitioned if shard is not None else lib.jh_cgls_solve), eng.native.handle
-        check(solve(h, u.handle, x.handle, 0 if x0 is None else 1, float(damp), float(atol), float(btol), int(maxiter),
-                    1 if force_maxiter else 0, C.byref(res), hist))
-    except JetsHipError as e:
-        if e.status != 4:                                       # JH_ERR_UNSUPPORTED comes before anything is touched: the generic loop
-            raise
-        return None
-    _count_chain_solve(chn)
-    _count_grid_solve(grid)
-    return _result(x, res, hist)
-
-
-def _native_team(eng, b, x0, damp, atol, btol, maxiter, overwrite_b, force_maxiter):
-    from ._ffi import LsqrResultC
-
-    T = eng.T
-    if os.environ.get("JETS_CGLS_NATIVE", "1") == "0" or any(n is None for n in T._natives):
-        return None
-    M = eng.team.world
-    x = eng.zeros_dom() if x0 is None else eng.copy(eng.zeros_dom(), x0)
-    u = b if overwrite_b else eng.copy(eng.zeros_rng(), b)
-    arr = lambda hs: (C.c_void_p * M)(*[h.value if hasattr(h, "value") else h for h in hs])
-    res = LsqrResultC()
-    hist = (C.c_double * builtins.max(2 * int(maxiter), 1))()
-    try:
-        check(lib.jh_cgls_solve_team(M, arr([n.handle for n in T._natives]), arr([u[k].handle for k in builtins.range(M)]),
-                                     arr([x[k].handle for k in builtins.range(M)]), 0 if x0 is None else 1, float(damp), float(atol), float(btol),
-                                     int(maxiter), 1 if force_maxiter else 0, C.byref(res), hist))
-    except JetsHipError as e:
-        if e.status != 4:
-            raise
-        return None
-    return _result(x, res, hist)
+    eng, b, x0 = _engine_for(A, b, x0)
+    res = _native_solve(eng, "cgls", b, x0, (damp, atol, btol), maxiter, force_maxiter, copy_b=not overwrite_b)
+    return res if res is not None else cgls_core(eng, b, x0, damp, atol, btol, maxiter, overwrite_b, force_maxiter)
 
 
 def cgls_core(eng, b, x0, damp, atol, btol, maxiter, overwrite_b=False, force_maxiter=False) -> LsqrResult:
@@ -168,78 +87,9 @@ def cgnr(A, b, x0=None, damp: float = 0.0, atol: float = 1e-6, btol: float = 1e-
     residual A'r is updated by recurrence in the domain), so: well-conditioned operators, throughput.  A device-native tall block
     operator runs behind the C ABI (jh_cgnr_solve / _partitioned / _team); anything else applies A then A' through the engines.
     The record: r2norm = sqrt(||r||^2 + damp^2 ||x||^2) from the recurrence, r1norm = ||r|| derived from it, arnorm = ||A'r - damp^2 x||."""
-    from .rowpart import RowPartitionedOp, TeamOp
-
-    if isinstance(A, TeamOp):
-        eng = _TeamEngine(A)
-        native = _native_cgnr_team(eng, b, x0, damp, atol, btol, maxiter, force_maxiter)
-        return native if native is not None else cgnr_core(eng, b, x0, damp, atol, btol, maxiter, force_maxiter)
-    if isinstance(A, RowPartitionedOp):
-        eng = _ShardEngine(A)
-        dom, rng = _j.domain(A.local_op), _j.range_(A.local_op)
-    else:
-        A = _unwrap_vec(A)
-        eng = _Engine(A)
-        dom, rng = _j.domain(A), _j.range_(A)
-    b = reshape(b, rng)
-    x0 = None if x0 is None else reshape(x0, dom)
-    native = _native_cgnr(eng, b, x0, damp, atol, btol, maxiter, force_maxiter)
-    return native if native is not None else cgnr_core(eng, b, x0, damp, atol, btol, maxiter, force_maxiter)
-
-
-def _native_cgnr(eng, b, x0, damp, atol, btol, maxiter, force_maxiter):
-    from ._ffi import LsqrResultC
-    from .rowpart import AbiComm
-
-    shard = getattr(eng, "shard", None)
-    nat = eng.native
-    chn = _chain_of(eng)
-    if nat is None and shard is None and chn is None and hasattr(eng, "A"):
-        from . import jetblock as _blk
-
-        nat = _blk._grid_native(eng.A)                 # round 6: N x (2 .. 4) grids of diagonals have a fused A'A too (jh_grid_normal.hip)
-    if os.environ.get("JETS_CGLS_NATIVE", "1") == "0" or (nat is None and chn is None):
-        return None
-    if shard is not None and not (isinstance(shard.comm, AbiComm) or shard.comm.world == 1):
-        return None
-    x = eng.zeros_dom() if x0 is None else eng.copy(eng.zeros_dom(), x0)
-    res = LsqrResultC()
-    hist = (C.c_double * builtins.max(2 * int(maxiter), 1))()
-    try:
-        if chn is not None:                                     # one FORWARD chain: its NORMAL program (jh_cgnr_solve_chain)
-            solve, h = lib.jh_cgnr_solve_chain, chn.fwd.handle
-        else:
-            solve, h = (lib.jh_cgnr_solve_partitioned if shard is not None else lib.jh_cgnr_solve), nat.handle
-        check(solve(h, b.handle, x.handle, 0 if x0 is None else 1, float(damp), float(atol), float(btol), int(maxiter),
-                    1 if force_maxiter else 0, C.byref(res), hist))
-    except JetsHipError as e:
-        if e.status != 4:
-            raise
-        return None
-    _count_chain_solve(chn)
-    return _result(x, res, hist)
-
-
-def _native_cgnr_team(eng, b, x0, damp, atol, btol, maxiter, force_maxiter):
-    from ._ffi import LsqrResultC
-
-    T = eng.T
-    if os.environ.get("JETS_CGLS_NATIVE", "1") == "0" or any(n is None for n in T._natives):
-        return None
-    M = eng.team.world
-    x = eng.zeros_dom() if x0 is None else eng.copy(eng.zeros_dom(), x0)
-    arr = lambda hs: (C.c_void_p * M)(*[h.value if hasattr(h, "value") else h for h in hs])
-    res = LsqrResultC()
-    hist = (C.c_double * builtins.max(2 * int(maxiter), 1))()
-    try:
-        check(lib.jh_cgnr_solve_team(M, arr([n.handle for n in T._natives]), arr([b[k].handle for k in builtins.range(M)]),
-                                     arr([x[k].handle for k in builtins.range(M)]), 0 if x0 is None else 1, float(damp), float(atol), float(btol),
-                                     int(maxiter), 1 if force_maxiter else 0, C.byref(res), hist))
-    except JetsHipError as e:
-        if e.status != 4:
-            raise
-        return None
-    return _result(x, res, hist)
+    eng, b, x0 = _engine_for(A, b, x0)
+    res = _native_solve(eng, "cgnr", b, x0, (damp, atol, btol), maxiter, force_maxiter, copy_b=False)     # (b is read, never written)
+    return res if res is not None else cgnr_core(eng, b, x0, damp, atol, btol, maxiter, force_maxiter)
 
 
 def cgnr_core(eng, b, x0, damp, atol, btol, maxiter, force_maxiter=False) -> LsqrResult:

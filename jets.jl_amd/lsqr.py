@@ -23,7 +23,7 @@ import ctypes as C
 import math
 import os
 
-from ._ffi import lib, check, JetsHipError
+from ._ffi import lib, check, JetsHipError, LsqrResultC
 from .arrays import zeros, lincomb_, norm, dot, copyto_, reshape, fill_
 
 
@@ -33,6 +33,7 @@ def _plain(coefs):
     return [float(c) for c in coefs]
 from . import jets as _j
 from . import jetblock as _blk
+from . import chains as _chn
 
 __all__ = ["lsqr", "lsqr_core", "LsqrResult"]
 
@@ -83,8 +84,6 @@ class _Engine:
         if self.native is None and type(self) is _Engine and isinstance(A, _j.JopLn):
             self.grid = _blk._grid_native(A)
         if self.native is None and type(self) is _Engine:
-            from . import chains as _chn
-
             sc = _chn.SolverChains(self.L)
             if sc.fwd is not None:
                 self.chains = sc
@@ -143,20 +142,27 @@ class _Engine:
         return math.sqrt(self._fwd_local(u, v, alpha, beta))
 
     def _step_local(self, u, v, alpha, beta):
-        """One pass: u <- alpha*(A v) + beta*u and w <- A'u (new u, un-normalised).  Returns (LOCAL ||u||^2, w) or None
-        when the operator has no fused step (then lsqr_core runs the two halves separately)."""
-        if self.native is None or not self.fused_step:
+        """One pass of jh_blockop_bidiag_step on the tall operator or the bare grid: u <- alpha*(A v) + beta*u and w <- A'u (new u,
+        un-normalised).  Returns (LOCAL ||u||^2, w) or None when there is no such operator (then lsqr_core runs the two halves separately).
+        When the library declines, the route is dropped for good: the grid (grid = None), or the tall operator's fused step (fused_step = False)."""
+        op = self.native if self.native is not None else self.grid
+        if op is None or not self.fused_step:
             return None
         if self._tmp_d is None:
             self._tmp_d = zeros(_j.domain(self.A))
         out = C.c_double(0)
         try:
-            check(lib.jh_blockop_bidiag_step(self.native.handle, u.handle, v.handle, self._tmp_d.handle, float(alpha), float(beta), C.byref(out)))
+            check(lib.jh_blockop_bidiag_step(op.handle, u.handle, v.handle, self._tmp_d.handle, float(alpha), float(beta), C.byref(out)))
         except JetsHipError as e:
-            if e.status != 4:
+            if e.status != 4:                                   # JH_ERR_UNSUPPORTED comes before anything is touched
                 raise
-            self.fused_step = False
+            if op is self.grid:
+                self.grid = None
+            else:
+                self.fused_step = False
             return None
+        if op is self.grid:
+            _chn.STATS["grid_step_calls"] += 1
         return out.value, self._tmp_d
 
     def step(self, u, v, alpha, beta):
@@ -167,29 +173,25 @@ class _Engine:
             nrm2 = self.chains.step(u, v, self._tmp_d, alpha, beta)
             if nrm2 is not None:
                 return math.sqrt(nrm2), self._tmp_d
-        if self.grid is not None and self.fused_step:
-            nrm2 = self._grid_step(u, v, alpha, beta)
-            if nrm2 is not None:
-                return math.sqrt(nrm2), self._tmp_d
         r = self._step_local(u, v, alpha, beta)
         return None if r is None else (math.sqrt(r[0]), r[1])
 
-    def _grid_step(self, u, v, alpha, beta):
-        """The grid's one-pass step into self._tmp_d; ||u||^2, or None when the library declines (the grid is then dropped: two halves from here on)."""
-        from . import chains as _chn
+    def native_solver(self, solver: str):
+        """The whole `solver` loop behind the C ABI ("lsqr", "cgls" or "cgnr"): (entry point, its leading arguments, the chains.STATS counters a
+        finished solve bumps), or None (lsqr_core / cgls_core / cgnr_core then run).  One FORWARD chain: jh_*_solve_chain on its handle; a bare
+        grid or the tall operator: jh_*_solve."""
+        if self.chains is not None and self.chains.fwd is not None:
+            fwd = self.chains.fwd
+            return getattr(lib, f"jh_{solver}_solve_chain"), (fwd.handle,), ("chain_solve_calls",) + (("grid_chain_calls",) if fwd.grid else ())
+        if self.grid is not None:
+            return getattr(lib, f"jh_{solver}_solve"), (self.grid.handle,), ("grid_solve_calls",) if solver != "cgnr" else ()
+        if self.native is not None:
+            return getattr(lib, f"jh_{solver}_solve"), (self.native.handle,), ()
+        return None
 
-        if self._tmp_d is None:
-            self._tmp_d = zeros(_j.domain(self.A))
-        out = C.c_double(0)
-        try:
-            check(lib.jh_blockop_bidiag_step(self.grid.handle, u.handle, v.handle, self._tmp_d.handle, float(alpha), float(beta), C.byref(out)))
-        except JetsHipError as e:
-            if e.status != 4:                                   # JH_ERR_UNSUPPORTED comes before anything is touched
-                raise
-            self.grid = None
-            return None
-        _chn.STATS["grid_step_calls"] += 1
-        return out.value
+    def vec_arg(self, x):
+        """A vector as the native solves take it."""
+        return x.handle
 
     def _chain_normal(self, y, p) -> float:
         """y = L'L p as ONE NORMAL chain (cgnr_core's hook); returns <p, y>.  Should the library decline the handle, A then A' through a range
@@ -270,6 +272,14 @@ class _ShardEngine(_Engine):
         lincomb_(v, _plain([alpha, beta]), [self._tmp_d, v])
         return float(norm(v))
 
+    def native_solver(self, solver: str):
+        """jh_*_solve_partitioned over the ABI's own communicator (AbiComm), or with one rank; None with a torch.distributed exchange."""
+        from .rowpart import AbiComm
+
+        if self.native is None or not (isinstance(self.shard.comm, AbiComm) or self.shard.comm.world == 1):
+            return None
+        return getattr(lib, f"jh_{solver}_solve_partitioned"), (self.native.handle,), ()
+
 
 class _TeamEngine:
     """ONE process, several contexts (rowpart.Team / TeamOp): vectors are rowpart.TeamVec -- range side: every member's
@@ -282,13 +292,25 @@ class _TeamEngine:
         self._tmp_d = None
         self._engines = [_Engine(A) for A in T.local_ops]     # per member: the fused local halves
         self.fused_step = os.environ.get("JETS_LSQR_FUSED_STEP", "1") != "0"
-        self.native = None                                    # jh_lsqr_solve* are per-rank loops: lsqr_core drives a team
+
+    def native_solver(self, solver: str):
+        """jh_*_solve_team: the whole loop over the team behind ONE call (what the Julia binding uses); None when a member has no native
+        operator."""
+        if any(n is None for n in self.T._natives):
+            return None
+        return getattr(lib, f"jh_{solver}_solve_team"), (self.team.world, self.T._handles(self.T._natives)), ()
+
+    def vec_arg(self, x):
+        return self.T._handles(x.members)
 
     def zeros_dom(self):
         return self.team.zeros(self.T.domain())
 
     def zeros_rng(self):
         return self.team.zeros(self.T.ranges())
+
+    def copy_of_rng(self, src):
+        return self.copy(self.zeros_rng(), src)
 
     def copy(self, dst, src):
         for k, _ in self.team.each():
@@ -332,118 +354,54 @@ def lsqr(A, b, x0=None, damp: float = 0.0, atol: float = 1e-6, btol: float = 1e-
     right-hand side and every rank returns the same x).  `overwrite_b=True` lets the solver use b's storage for
     the Lanczos vector u (at the headline size b is 64 GiB).  `force_maxiter=True` keeps iterating past every
     stopping rule (throughput measurements only)."""
+    eng, b, x0 = _engine_for(A, b, x0)
+    res = _native_solve(eng, "lsqr", b, x0, (damp, atol, btol, conlim), maxiter, force_maxiter, copy_b=not overwrite_b)
+    return res if res is not None else lsqr_core(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, force_maxiter)
+
+
+def _engine_for(A, b, x0):
+    """The engine of a solver's operator, with b and x0 in its spaces: one GPU (vec(A) unwrapped), a rowpart.RowPartitionedOp (this rank's
+    rows) or a rowpart.TeamOp (b, x0: TeamVecs, as given)."""
     from .rowpart import RowPartitionedOp, TeamOp
 
-    if isinstance(A, TeamOp):                            # one process, several contexts: b and the result are TeamVecs
-        eng = _TeamEngine(A)
-        native = _native_team_solve(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, force_maxiter)
-        if native is not None:
-            return native
-        return lsqr_core(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, force_maxiter)
+    if isinstance(A, TeamOp):
+        return _TeamEngine(A), b, x0
     if isinstance(A, RowPartitionedOp):
-        eng = _ShardEngine(A)
-        dom, rng = _j.domain(A.local_op), _j.range_(A.local_op)
+        eng, op = _ShardEngine(A), A.local_op
     else:
-        A = _unwrap_vec(A)
-        eng = _Engine(A)
-        dom, rng = _j.domain(A), _j.range_(A)
-    b = reshape(b, rng)
-    x0 = None if x0 is None else reshape(x0, dom)
-    native = _native_solve(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, force_maxiter)
-    if native is not None:
-        return native
-    return lsqr_core(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, force_maxiter)
+        op = _unwrap_vec(A)
+        eng = _Engine(op)
+    return eng, reshape(b, _j.range_(op)), None if x0 is None else reshape(x0, _j.domain(op))
 
 
-def _native_solve(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, force_maxiter):
-    """The whole loop behind the C ABI (jh_lsqr_solve: the same recurrences in C++ over the one-pass step) for a
-    device-native tall diagonal operator on one GPU, or row-partitioned over the ABI's own RCCL communicator (AbiComm).
-    None when it does not apply (generic operators, torch.distributed exchange, JETS_LSQR_NATIVE=0): lsqr_core then runs."""
-    from ._ffi import LsqrResultC
-    from .rowpart import AbiComm
-
-    chn = _chain_of(eng)
-    grid = _grid_of(eng)
-    if os.environ.get("JETS_LSQR_NATIVE", "1") == "0" or (eng.native is None and chn is None and grid is None) or not eng.fused_step:
+def _native_solve(eng, solver, b, x0, tols, maxiter, force_maxiter, copy_b):
+    """The whole loop of `solver` ("lsqr", "cgls", "cgnr") behind ONE ABI call, the same recurrences in C++ (jh_lsqr.hip), on the engine's
+    native target (`eng.native_solver`).  `tols` are the floats between x0's flag and maxiter: (damp, atol, btol, conlim) for LSQR, (damp,
+    atol, btol) for CGLS and CGNR.  LSQR and CGLS iterate on u, a copy of b (`copy_b`) or b's own storage; CGNR reads b and never writes it.
+    None when it does not apply (no native target, JETS_LSQR_NATIVE=0 / JETS_LSQR_FUSED_STEP=0 for LSQR, JETS_CGLS_NATIVE=0 for CGLS and
+    CGNR) or the library declines before anything is touched (JH_ERR_UNSUPPORTED): the Python loop then runs."""
+    if solver == "lsqr":
+        if os.environ.get("JETS_LSQR_NATIVE", "1") == "0" or not eng.fused_step:
+            return None
+    elif os.environ.get("JETS_CGLS_NATIVE", "1") == "0":
         return None
-    shard = getattr(eng, "shard", None)
-    if shard is not None and not (isinstance(shard.comm, AbiComm) or shard.comm.world == 1):
+    target = eng.native_solver(solver)
+    if target is None:
         return None
+    solve, lead, counters = target
     x = eng.zeros_dom() if x0 is None else eng.copy(eng.zeros_dom(), x0)
-    u = b if overwrite_b else (eng.copy_of_rng(b) if hasattr(eng, "copy_of_rng") else eng.copy(eng.zeros_rng(), b))
+    u = eng.copy_of_rng(b) if copy_b else b
     res = LsqrResultC()
     hist = (C.c_double * builtins.max(2 * int(maxiter), 1))()
     try:
-        # a rank-local operator is solved locally even while an AbiComm is alive; only a RowPartitionedOp is a collective solve
-        if chn is not None:                                     # one FORWARD chain: jh_lsqr_solve_chain iterates on its one-pass step
-            solve, h = lib.jh_lsqr_solve_chain, chn.fwd.handle
-        elif grid is not None:                                  # a bare grid: jh_lsqr_solve iterates on the grid's one-pass step
-            solve, h = lib.jh_lsqr_solve, grid.handle
-        else:
-            solve, h = (lib.jh_lsqr_solve_partitioned if shard is not None else lib.jh_lsqr_solve), eng.native.handle
-        check(solve(h, u.handle, x.handle, 0 if x0 is None else 1, float(damp), float(atol), float(btol),
-                    float(conlim), int(maxiter), 1 if force_maxiter else 0, C.byref(res), hist))
-    except JetsHipError as e:
-        if e.status != 4:                                       # JH_ERR_UNSUPPORTED is raised before anything is touched: generic path
-            raise
-        return None
-    _count_chain_solve(chn)
-    _count_grid_solve(grid)
-    history = [(k + 1, hist[2 * k], hist[2 * k + 1]) for k in builtins.range(res.itn)]
-    return LsqrResult(x, res.istop, res.itn, res.r1norm, res.r2norm, res.anorm, res.acond, res.arnorm, res.xnorm, history)
-
-
-def _grid_of(eng):
-    """The one-GPU engine's bare grid (the NativeBlockOp of an N x (2 .. 4) block operator) when the native solve runs on it, else None."""
-    grid = getattr(eng, "grid", None)
-    return grid if grid is not None and eng.native is None and _chain_of(eng) is None and getattr(eng, "shard", None) is None else None
-
-
-def _count_grid_solve(grid):
-    if grid is not None:
-        from . import chains as _chn
-
-        _chn.STATS["grid_solve_calls"] += 1
-
-
-def _chain_of(eng):
-    """The one-GPU engine's FORWARD chain (chains.SolverChains) when the solve runs on it, else None."""
-    chn = getattr(eng, "chains", None)
-    return chn if chn is not None and chn.fwd is not None and eng.native is None and getattr(eng, "shard", None) is None else None
-
-
-def _count_chain_solve(chn):
-    if chn is not None:
-        from . import chains as _chn
-
-        _chn.STATS["chain_solve_calls"] += 1
-        if chn.fwd.grid:
-            _chn.STATS["grid_chain_calls"] += 1
-
-
-def _native_team_solve(eng, b, x0, damp, atol, btol, conlim, maxiter, overwrite_b, force_maxiter):
-    """jh_lsqr_solve_team: the whole loop over a single-process team behind ONE call (what the Julia binding uses).  None when a
-    member has no native tall operator or JETS_LSQR_NATIVE=0: lsqr_core then drives the team from here."""
-    from ._ffi import LsqrResultC
-    from .rowpart import TeamVec
-
-    T = eng.T
-    if os.environ.get("JETS_LSQR_NATIVE", "1") == "0" or not eng.fused_step or any(n is None for n in T._natives):
-        return None
-    M = eng.team.world
-    x = eng.zeros_dom() if x0 is None else eng.copy(eng.zeros_dom(), x0)
-    u = b if overwrite_b else eng.copy(eng.zeros_rng(), b)
-    arr = lambda hs: (C.c_void_p * M)(*[h.value if hasattr(h, "value") else h for h in hs])
-    res = LsqrResultC()
-    hist = (C.c_double * builtins.max(2 * int(maxiter), 1))()
-    try:
-        check(lib.jh_lsqr_solve_team(M, arr([n.handle for n in T._natives]), arr([u[k].handle for k in builtins.range(M)]),
-                                     arr([x[k].handle for k in builtins.range(M)]), 0 if x0 is None else 1, float(damp), float(atol), float(btol),
-                                     float(conlim), int(maxiter), 1 if force_maxiter else 0, C.byref(res), hist))
+        check(solve(*lead, eng.vec_arg(u), eng.vec_arg(x), 0 if x0 is None else 1, *[float(t) for t in tols], int(maxiter),
+                    1 if force_maxiter else 0, C.byref(res), hist))
     except JetsHipError as e:
         if e.status != 4:
             raise
         return None
+    for k in counters:
+        _chn.STATS[k] += 1
     history = [(k + 1, hist[2 * k], hist[2 * k + 1]) for k in builtins.range(res.itn)]
     return LsqrResult(x, res.istop, res.itn, res.r1norm, res.r2norm, res.anorm, res.acond, res.arnorm, res.xnorm, history)
 

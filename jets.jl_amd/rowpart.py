@@ -157,7 +157,7 @@ class RowPartitionedOp:
         self.part, self.local_op, self.comm = part, local_op, comm
         self._mul, self._mul_adj, self._dot, self._norm = local_mul, local_mul_adj, local_dot, local_norm
         self._pipelined_adj = pipelined_adj   # optional: local adjoint and all-reduce pipelined chunk by chunk
-        self._pipelined_step = pipelined_step  # optional: one-pass Golub-Kahan step, its w all-reduced chunk by chunk
+        self._pipelined_step = pipelined_step  # optional: one-pass Golub-Kahan step, its w all-reduced chunk by chunk; returns the global ||u||^2
         self._pipelined_normal = pipelined_normal  # optional: the fused A'A, its result all-reduced chunk by chunk
         self._local_normal = local_normal      # optional: this rank's L'L m in one fused pass (a weighted shard's NORMAL chain), no range temporary
         self._chains = chains                  # the device handles a weighted shard's routes hold (released by close())
@@ -196,12 +196,7 @@ class RowPartitionedOp:
         operator has no ranged one-pass kernel (the caller then runs the step in one piece)."""
         if self._pipelined_step is None or not (self.comm.world > 1 or force_collective):
             return None
-        local = self._pipelined_step(u_local, v, w, alpha, beta)
-        if local is None:
-            return None
-        if isinstance(local, tuple):                          # (value, True): already summed over the ranks (jh_comm_allreduce_normsq)
-            return local[0]
-        return self.comm.all_reduce_scalars([local], "sum")[0]
+        return self._pipelined_step(u_local, v, w, alpha, beta)
 
     def mul_(self, d_local, m):
         """d_local = A[rows of this rank] m   -- no communication."""
@@ -275,169 +270,182 @@ class _ShardChains:
         self.cache.close()
 
 
-def _ranged_chain(h, out, x, nchunks: int, enqueue_exchange, join) -> bool:
-    """A weighted shard's chain in `nchunks` element ranges (jh_chain_apply_range, accumulate 0: with +-1 every rank would add `out` once), the
-    exchange of a finished range enqueued behind its kernel.  False when there is no handle, or the library declines before anything was
-    enqueued (the caller then takes today's route)."""
-    from ._ffi import JetsHipError
-
-    if h is None:
-        return False
-    done = 0
-    try:
-        for lo, cnt in _chunk_bounds(out.length(), nchunks):
-            h.apply_range(out, x, lo, cnt, 0)
-            enqueue_exchange(lo, cnt)
-            done += 1
-    except JetsHipError as e:
-        if e.status == 4 and done == 0:                       # JH_ERR_UNSUPPORTED before anything was enqueued
-            return False
-        raise
-    join()
-    return True
-
-
 def for_device(part: RowPartition, local_op, comm=None) -> RowPartitionedOp:
     """Product wiring: HIP kernels for the local work, RCCL for the exchange -- through torch.distributed's "nccl"
     backend (default; the all-reduce is ordered against the library's HIP stream with torch.cuda.ExternalStream)
-    or through the C ABI's own RCCL entry points when an AbiComm is passed."""
-    from . import device as _device
+    or through the C ABI's own RCCL entry points when an AbiComm is passed.  Any other `comm` gets the unpipelined routes."""
     from .arrays import dot, norm
     from .jets import mul_, adjoint
 
-    if comm is not None:
-        if isinstance(comm, AbiComm):
-            return _for_device_abi(part, local_op, comm)
-        sc = _ShardChains(local_op)
-        return RowPartitionedOp(part, local_op, comm, lambda d, A, m: mul_(d, A, m), lambda m, A, d: mul_(m, adjoint(A), d), dot, norm,
-                                local_normal=sc.local_normal if sc.has_normal else None, chains=sc)
-    import torch
+    xch = None
+    if comm is None:
+        xch = _TorchExchange()
+        comm = xch.comm
+    elif isinstance(comm, AbiComm):
+        xch = _AbiExchange()
+    sc = _ShardChains(local_op)
+    routes = {} if xch is None else _pipelined_routes(xch, local_op, sc)
+    return RowPartitionedOp(part, local_op, comm, lambda d, A, m: mul_(d, A, m), lambda m, A, d: mul_(m, adjoint(A), d), dot, norm,
+                            local_normal=sc.local_normal if sc.has_normal else None, chains=sc, **routes)
 
-    ext = torch.cuda.ExternalStream(_device.stream_handle(), device=torch.device("cuda", _device.init()))
 
-    def as_tensor(x):
+class _TorchExchange:
+    """The exchange of the torch.distributed wiring: a range of a vector is all-reduced on RCCL's stream (torch.cuda.ExternalStream of
+    the library stream: RCCL's stream waits for the library stream up to there); join makes the library stream wait for every range."""
+
+    def __init__(self):
+        import torch
+        import torch.distributed as dist
+
+        from . import device as _device
+
+        self._torch, self._dist, self._device = torch, dist, _device
+        self._ext = torch.cuda.ExternalStream(_device.stream_handle(), device=torch.device("cuda", _device.init()))
+        self.comm = Comm(self._as_tensor, lambda: torch.cuda.stream(self._ext))
+        self._views = {}    # id(vector) -> (vector, flat torch view): a solver exchanges the same one or two vectors every iteration
+        self._t, self._works = None, []
+
+    def _as_tensor(self, x):
         # RCCL needs a contiguous tensor: hand it the flat 1-D view of the slab (shares memory with x)
         flat = x if len(x.shape) == 1 else x.reshape((x.length(),))
-        t = torch.as_tensor(flat, device=torch.device("cuda", _device.init()))
+        t = self._torch.as_tensor(flat, device=self._torch.device("cuda", self._device.init()))
         t._jets_owner = flat  # keep the view alive while torch holds the pointer
         return t
 
-    def stream_ctx():
-        return torch.cuda.stream(ext)
+    def ready(self) -> bool:
+        return self._dist.is_initialized()
 
-    comm = Comm(as_tensor, stream_ctx)
+    def open(self, x):
+        """Start the exchange of `x`, range by range."""
+        hit = self._views.get(id(x))
+        if hit is None or hit[0] is not x:
+            if len(self._views) >= 8:                         # bounded: a view pins its vector (64 MiB at the headline size)
+                self._views.clear()
+            hit = self._views[id(x)] = (x, self._as_tensor(x))
+        self._t, self._works = hit[1], []
 
+    def send(self, lo: int, cnt: int):
+        with self._torch.cuda.stream(self._ext):
+            self._works.append(self._dist.all_reduce(self._t[lo:lo + cnt], op=self._dist.ReduceOp.SUM, async_op=True))
+
+    def join(self):
+        with self._torch.cuda.stream(self._ext):
+            for w in self._works:
+                w.wait()
+
+    def normsq(self) -> float:
+        """The step's global ||u||^2: the one read-back of the library stream's accumulator (kernels only, not the exchange), the join,
+        then the scalar all-reduce."""
+        from ._ffi import lib, check
+
+        out = C.c_double(0)
+        check(lib.jh_normsq_read(C.byref(out)))
+        self.join()
+        return self.comm.all_reduce_scalars([out.value], "sum")[0]
+
+
+class _AbiExchange:
+    """The exchange of the AbiComm wiring (what a host without torch.distributed gets): the C ABI's own communicator and exchange stream."""
+
+    def __init__(self):
+        from ._ffi import lib, check
+
+        self._lib, self._check = lib, check
+        self._x = None
+
+    def ready(self) -> bool:
+        return True                                           # (with one rank the caller only comes here when forced: validation)
+
+    def open(self, x):
+        self._x = x
+
+    def send(self, lo: int, cnt: int):
+        self._check(self._lib.jh_comm_allreduce_sum_range(self._x.handle, lo, cnt))
+
+    def join(self):
+        self._check(self._lib.jh_comm_join())
+
+    def normsq(self) -> float:
+        """The step's global ||u||^2 (jh_comm_allreduce_normsq): kernels and ranged all-reduces are complete on return."""
+        out = C.c_double(0)
+        self._check(self._lib.jh_comm_allreduce_normsq(C.byref(out)))
+        return out.value
+
+
+def _pipelined(xch, out, nchunks: int, kernel, finish=None):
+    """kernel(lo, cnt) for every element range of `out`, the exchange of a finished range (xch.send) enqueued behind its kernel, so it
+    runs under the next range's kernel; then finish() -- by default xch.join(), and True.  None when the library declines
+    (JH_ERR_UNSUPPORTED) before anything was enqueued: the caller then takes its unpipelined route.  A decline after that raises."""
+    from ._ffi import JetsHipError
+
+    xch.open(out)
+    done = 0
+    try:
+        for lo, cnt in _chunk_bounds(out.length(), nchunks):
+            kernel(lo, cnt)
+            xch.send(lo, cnt)
+            done += 1
+    except JetsHipError as e:
+        if e.status == 4 and done == 0:
+            return None
+        raise
+    if finish is not None:
+        return finish()
+    xch.join()
+    return True
+
+
+def _pipelined_routes(xch, local_op, sc) -> dict:
+    """RowPartitionedOp's pipelined adjoint, fused A'A and one-pass step over the exchange `xch` (_TorchExchange or _AbiExchange), in
+    JETS_AR_CHUNKS element ranges."""
     import os
 
-    import torch.distributed as dist
-
-    from ._ffi import lib, check, JetsHipError
+    from ._ffi import lib, check
     from . import jetblock as _blk
 
     nchunks = int(os.environ.get("JETS_AR_CHUNKS", "4"))
-    views = {}      # id(vector) -> (vector, flat torch view): a solver exchanges the same one or two vectors every iteration
-
-    def tensor_of(x):
-        hit = views.get(id(x))
-        if hit is None or hit[0] is not x:
-            if len(views) >= 8:                               # bounded: a view pins its vector (64 MiB at the headline size)
-                views.clear()
-            hit = views[id(x)] = (x, as_tensor(x))
-        return hit[1]
 
     def native_of(A):
-        if nchunks <= 1 or not dist.is_initialized() or not _blk.isblockop(A):
+        if nchunks <= 1 or not xch.ready() or not _blk.isblockop(A):
             return None
         jt = A.jet
         return _blk._native_op(jt.s.get("_native"), jt.s["ops"], jt.rng.eltype())
 
-    def chunk_bounds(n):
-        return _chunk_bounds(n, nchunks)
-
-    def exchange(t, lo, cnt, works):
-        with torch.cuda.stream(ext):                          # RCCL's stream waits for the library stream up to here
-            works.append(dist.all_reduce(t[lo:lo + cnt], op=dist.ReduceOp.SUM, async_op=True))
-
-    def join(works):
-        with torch.cuda.stream(ext):
-            for w in works:
-                w.wait()                                      # the library stream waits for every chunk's all-reduce
-
-    sc = _ShardChains(local_op)
-
-    def weighted(out, x, h) -> bool:
-        """A weighted shard's ADJOINT / NORMAL chain range by range, each range's all-reduce on RCCL's stream behind it."""
-        if nchunks <= 1 or not dist.is_initialized():
+    def weighted(out, x, h):
+        """A weighted shard's ADJOINT / NORMAL chain range by range (jh_chain_apply_range, accumulate 0: with +-1 every rank would add `out`
+        once).  False when there is no handle."""
+        if nchunks <= 1 or not xch.ready() or h is None:
             return False
-        t = tensor_of(out)
-        works = []
-        return _ranged_chain(h, out, x, nchunks, lambda lo, cnt: exchange(t, lo, cnt, works), lambda: join(works))
+        return _pipelined(xch, out, nchunks, lambda lo, cnt: h.apply_range(out, x, lo, cnt, 0))
 
-    def pipelined_adj(m, A, d) -> bool:
-        """Local adjoint in `nchunks` element ranges (jh_blockop_mul_adj_range); the all-reduce of a finished range
-        runs on RCCL's stream while the kernel of the next range runs on the library stream.  Same values as the
-        unpipelined path.  Returns False when the operator has no ranged kernel (then the caller does it in one piece)."""
+    def pipelined_adj(m, A, d):
+        """Local adjoint in `nchunks` element ranges (jh_blockop_mul_adj_range), each range's all-reduce under the next range's kernel.
+        Same values as the unpipelined path.  Falsy when the operator has no ranged kernel (then the caller does it in one piece)."""
         nat = native_of(A)
         if nat is None:
             return A is local_op and sc.has_adj and weighted(m, d, sc.adjoint())
-        t = tensor_of(m)
-        works = []
-        try:
-            for lo, cnt in chunk_bounds(m.length()):
-                check(lib.jh_blockop_mul_adj_range(nat.handle, m.handle, d.handle, lo, cnt))
-                exchange(t, lo, cnt, works)
-        except JetsHipError as e:
-            if e.status == 4 and not works:                   # JH_ERR_UNSUPPORTED before anything was enqueued
-                return False
-            raise
-        join(works)
-        return True
+        return _pipelined(xch, m, nchunks, lambda lo, cnt: check(lib.jh_blockop_mul_adj_range(nat.handle, m.handle, d.handle, lo, cnt)))
 
-    def pipelined_normal(y, A, m) -> bool:
+    def pipelined_normal(y, A, m):
         """The fused A'A in `nchunks` element ranges (jh_blockop_normal_mul_range), exchanged like the adjoint's."""
         nat = native_of(A)
         if nat is None:
             return A is local_op and sc.has_normal and weighted(y, m, sc.normal())
-        t = tensor_of(y)
-        works = []
-        try:
-            for lo, cnt in chunk_bounds(y.length()):
-                check(lib.jh_blockop_normal_mul_range(nat.handle, y.handle, m.handle, lo, cnt))
-                exchange(t, lo, cnt, works)
-        except JetsHipError as e:
-            if e.status == 4 and not works:
-                return False
-            raise
-        join(works)
-        return True
+        return _pipelined(xch, y, nchunks, lambda lo, cnt: check(lib.jh_blockop_normal_mul_range(nat.handle, y.handle, m.handle, lo, cnt)))
 
     def pipelined_step(u, v, w, alpha, beta):
-        """jh_blockop_bidiag_step in `nchunks` element ranges, enqueued back to back: every range adds its share of ||u||^2
-        to a device-side accumulator (jh_normsq_reset / normsq == NULL / jh_normsq_read), so the host synchronises ONCE per
-        step, after the last range, while the all-reduces of the finished ranges of w run under the later kernels.  Returns
-        the local ||u||^2, or None when the operator has no ranged one-pass kernel."""
+        """jh_blockop_bidiag_step in `nchunks` element ranges, enqueued back to back: every range adds its share of ||u||^2 to a device-side
+        accumulator (jh_normsq_reset / normsq == NULL), so the host synchronises ONCE per step, after the last range (xch.normsq), while the
+        all-reduces of the finished ranges of w run under the later kernels.  Returns the GLOBAL ||u||^2, or None when the operator has no
+        ranged one-pass kernel."""
         nat = native_of(local_op)
         if nat is None:
             return None
-        t = tensor_of(w)
-        works = []
-        out = C.c_double(0)
-        try:
-            check(lib.jh_normsq_reset())
-            for lo, cnt in chunk_bounds(w.length()):
-                check(lib.jh_blockop_bidiag_step_range(nat.handle, u.handle, v.handle, w.handle, float(alpha), float(beta), lo, cnt, None))
-                exchange(t, lo, cnt, works)
-        except JetsHipError as e:
-            if e.status == 4 and not works:
-                return None
-            raise
-        check(lib.jh_normsq_read(C.byref(out)))                # the one read-back (library stream: kernels only, not the exchange)
-        join(works)
-        return out.value
+        check(lib.jh_normsq_reset())
+        return _pipelined(xch, w, nchunks, lambda lo, cnt: check(lib.jh_blockop_bidiag_step_range(
+            nat.handle, u.handle, v.handle, w.handle, float(alpha), float(beta), lo, cnt, None)), finish=xch.normsq)
 
-    return RowPartitionedOp(part, local_op, comm, lambda d, A, m: mul_(d, A, m), lambda m, A, d: mul_(m, adjoint(A), d), dot, norm,
-                            pipelined_adj=pipelined_adj, pipelined_step=pipelined_step, pipelined_normal=pipelined_normal,
-                            local_normal=sc.local_normal if sc.has_normal else None, chains=sc)
+    return dict(pipelined_adj=pipelined_adj, pipelined_step=pipelined_step, pipelined_normal=pipelined_normal)
 
 
 def _chunk_bounds(n: int, nchunks: int):
@@ -448,92 +456,6 @@ def _chunk_bounds(n: int, nchunks: int):
         cnt = builtins.min(step, n - lo)
         yield lo, cnt
         lo += cnt
-
-
-def _for_device_abi(part: RowPartition, local_op, comm: AbiComm) -> RowPartitionedOp:
-    """The same wiring over the C ABI's own communicator and exchange stream (jh_comm_allreduce_sum_range / jh_comm_join /
-    jh_comm_allreduce_normsq): what a host without torch.distributed gets -- the pipelined adjoint and the pipelined one-pass
-    step with ONE host synchronisation per step."""
-    import os
-
-    from ._ffi import lib, check, JetsHipError
-    from . import jetblock as _blk
-    from .arrays import dot, norm
-    from .jets import mul_, adjoint
-
-    nchunks = int(os.environ.get("JETS_AR_CHUNKS", "4"))
-
-    def native_of(A):
-        if nchunks <= 1 or not _blk.isblockop(A):             # (with one rank the caller only comes here when forced: validation)
-            return None
-        jt = A.jet
-        return _blk._native_op(jt.s.get("_native"), jt.s["ops"], jt.rng.eltype())
-
-    sc = _ShardChains(local_op)
-
-    def weighted(out, x, h) -> bool:
-        """A weighted shard's ADJOINT / NORMAL chain range by range, each range all-reduced on the communicator's stream behind it."""
-        if nchunks <= 1:
-            return False
-        return _ranged_chain(h, out, x, nchunks, lambda lo, cnt: check(lib.jh_comm_allreduce_sum_range(out.handle, lo, cnt)),
-                             lambda: check(lib.jh_comm_join()))
-
-    def pipelined_adj(m, A, d) -> bool:
-        nat = native_of(A)
-        if nat is None:
-            return A is local_op and sc.has_adj and weighted(m, d, sc.adjoint())
-        done = 0
-        try:
-            for lo, cnt in _chunk_bounds(m.length(), nchunks):
-                check(lib.jh_blockop_mul_adj_range(nat.handle, m.handle, d.handle, lo, cnt))
-                check(lib.jh_comm_allreduce_sum_range(m.handle, lo, cnt))
-                done += 1
-        except JetsHipError as e:
-            if e.status == 4 and done == 0:
-                return False
-            raise
-        check(lib.jh_comm_join())
-        return True
-
-    def pipelined_normal(y, A, m) -> bool:
-        nat = native_of(A)
-        if nat is None:
-            return A is local_op and sc.has_normal and weighted(y, m, sc.normal())
-        done = 0
-        try:
-            for lo, cnt in _chunk_bounds(y.length(), nchunks):
-                check(lib.jh_blockop_normal_mul_range(nat.handle, y.handle, m.handle, lo, cnt))
-                check(lib.jh_comm_allreduce_sum_range(y.handle, lo, cnt))
-                done += 1
-        except JetsHipError as e:
-            if e.status == 4 and done == 0:
-                return False
-            raise
-        check(lib.jh_comm_join())
-        return True
-
-    def pipelined_step(u, v, w, alpha, beta):
-        nat = native_of(local_op)
-        if nat is None:
-            return None
-        out = C.c_double(0)
-        done = 0
-        try:
-            check(lib.jh_normsq_reset())
-            for lo, cnt in _chunk_bounds(w.length(), nchunks):
-                check(lib.jh_blockop_bidiag_step_range(nat.handle, u.handle, v.handle, w.handle, float(alpha), float(beta), lo, cnt, None))
-                check(lib.jh_comm_allreduce_sum_range(w.handle, lo, cnt))
-                done += 1
-        except JetsHipError as e:
-            if e.status == 4 and done == 0:
-                return None
-            raise
-        check(lib.jh_comm_allreduce_normsq(C.byref(out)))     # global ||u||^2; kernels and ranged all-reduces are complete on return
-        return (out.value, True)
-
-    return RowPartitionedOp(part, local_op, comm, lambda d, A, m: mul_(d, A, m), lambda m, A, d: mul_(m, adjoint(A), d), dot, norm,
-                            pipelined_adj=pipelined_adj, pipelined_step=pipelined_step, pipelined_normal=pipelined_normal,
-                            local_normal=sc.local_normal if sc.has_normal else None, chains=sc)
 
 
 # ------------------------------------------------------------------ ONE process, several contexts -------------------------
