@@ -2,7 +2,19 @@
 package / C ABI) and in the CPU oracle."""
 from __future__ import annotations
 
+import importlib.util
+import os
+
 import numpy as np
+
+
+def load_tool(name):
+    """tools/<name>.py as a module (tools/ is no package: the stand-alone programs there are also the shared code of some tests)."""
+    spec = importlib.util.spec_from_file_location(name, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
 
 DTYPES = [np.float32, np.float64, np.complex64, np.complex128]
 SEED_A, SEED_M, SEED_D = 1, 2, 3  # SURVEY.md 8d

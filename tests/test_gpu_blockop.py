@@ -121,9 +121,10 @@ def test_dot_product_test_tall(Jets, oracle, dt):
 
 
 # ---------------------------------------------------------------------------------- general path
-def _mixed_ops(Jets, oracle, dt, kinds, lens_r, lens_c, seed=21):
+def _mixed_ops(Jets, oracle, dt, kinds, lens_r, lens_c, seed=21, coeff=None):
     """Build the same nrow x ncol mixed operator on the device and in the oracle. kinds[i][j] in
-    {'zero','identity','scale','diag','diag_adj'}; elementwise blocks need lens_r[i] == lens_c[j]."""
+    {'zero','identity','scale','diag','diag_adj'}; elementwise blocks need lens_r[i] == lens_c[j].
+    coeff(i, j, n): the host coefficients of the diagonal block (i, j) (default: the counter generator's U[0,1) streams)."""
     dev_rows, ora_rows = [], []
     for i, row in enumerate(kinds):
         dr, orow = [], []
@@ -140,9 +141,13 @@ def _mixed_ops(Jets, oracle, dt, kinds, lens_r, lens_c, seed=21):
                 orow.append(oracle.Block("scale", nr, scale=a))
             else:
                 stream = 100 * i + j
-                dg = Jets.rand(dom, seed=seed, stream=stream)
+                if coeff is None:
+                    dg, hc = Jets.rand(dom, seed=seed, stream=stream), u01(oracle, dt, seed, stream, nr)
+                else:
+                    hc = np.ascontiguousarray(coeff(i, j, nr), dtype=dt)
+                    dg = Jets.from_numpy(hc, dom)
                 op = Jets.JopDiagonal(dg)
-                hb = oracle.Block("diag", nr, coeff=u01(oracle, dt, seed, stream, nr), adjoint=(k == "diag_adj"))
+                hb = oracle.Block("diag", nr, coeff=hc, adjoint=(k == "diag_adj"))
                 dr.append(op.H if k == "diag_adj" else op); orow.append(hb)
         dev_rows.append(dr); ora_rows.append(orow)
     return Jets.blockop(dev_rows), ora_rows
@@ -619,7 +624,9 @@ def test_special_values_go_through_every_kernel_family_like_on_the_cpu(Jets, ora
     a + - + sum, dense children, jh_lincomb and the compiled broadcast give the oracle's value element by element (0 * Inf = NaN
     where the reference multiplies, an untouched 0 where it skips a zero block; complex products by the four-multiplication
     formula; REAL scalars on complex data part by part, as Julia's a::Real * z).  Bit for bit except for the payload of a NaN.
-    The checks live in tools/check_specials.py (also a stand-alone program)."""
+    The checks live in tools/check_specials.py (also a stand-alone program): run_checks, called here.  The families written later --
+    fused tall chains, the chain and grid Golub-Kahan steps, fused A'A and chains of N x K grids, the per-block reductions, the split
+    walk -- are run_fused_checks of the same tool, case by case in tests/test_gpu_specials_fused.py."""
     import importlib.util
     import os
 

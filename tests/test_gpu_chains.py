@@ -26,15 +26,22 @@ def _kinds(nrow, name):
 class Rig:
     """One tall operator A (nrow x 1, blocks of n elements) with two weight vectors on its range and two diagonals on its domain, on the device and
     in the oracle.  A chain is a list of tokens in APPLICATION order: "A", "At", ("W", k, conj), ("M", k, conj), ("s", a), ("Wb", k, conj) (the k-th
-    weights as a block-diagonal block operator), ("I",) identity on the domain, ("opaque",) a user-written closure on the domain (d .= 2 .* m)."""
+    weights as a block-diagonal block operator), ("I",) identity on the domain, ("opaque",) a user-written closure on the domain (d .= 2 .* m).
+    data(tag, n): host arrays in place of the counter generator's U[0,1) streams -- tag ("A", i, 0) the coefficients of row i, ("w", k) the k-th
+    weights (nrow * n elements), ("c", k) the k-th domain diagonal; kinds: the rows' kinds (a list of one-element lists), overriding `name`."""
 
-    def __init__(self, J, oracle, dt, nrow, n, name="diag", seed=31, with_wb=True):
+    def __init__(self, J, oracle, dt, nrow, n, name="diag", seed=31, with_wb=True, data=None, kinds=None):
         self.J, self.o, self.dt, self.nrow, self.n = J, oracle, dt, nrow, n
-        self.A, self.ora = _mixed_ops(J, oracle, dt, _kinds(nrow, name), [n] * nrow, [n], seed=seed)
+        self.A, self.ora = _mixed_ops(J, oracle, dt, kinds or _kinds(nrow, name), [n] * nrow, [n], seed=seed,
+                                      coeff=None if data is None else (lambda i, j, nr: data(("A", i, j), nr)))
         R, D = J.range(self.A), J.domain(self.A)
-        self.w = [J.rand(R, seed=seed + 1 + k, stream=0) for k in range(2)]
+        if data is None:
+            self.w = [J.rand(R, seed=seed + 1 + k, stream=0) for k in range(2)]
+            self.c = [J.rand(D, seed=seed + 5 + k, stream=0) for k in range(2)]
+        else:
+            self.w = [J.from_numpy(np.ascontiguousarray(data(("w", k), nrow * n), dtype=dt), R) for k in range(2)]
+            self.c = [J.from_numpy(np.ascontiguousarray(data(("c", k), n), dtype=dt), D) for k in range(2)]
         self.hw = [[b.copy() for b in np.split(w.to_numpy(), nrow)] for w in self.w]
-        self.c = [J.rand(D, seed=seed + 5 + k, stream=0) for k in range(2)]
         self.hc = [c.to_numpy().ravel(order="F").copy() for c in self.c]
         self.W = [J.JopDiagonal(w) for w in self.w]
         self.M = [J.JopDiagonal(c) for c in self.c]

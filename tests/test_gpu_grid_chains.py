@@ -26,15 +26,22 @@ def _grid_kinds(nrow, ncol, mixed):
 
 class GridRig:
     """An N x K grid A (blocks of n elements) with two weight vectors on its range, two diagonals on its domain (K n elements) and a block-diagonal
-    block operator of weights, on the device and in the oracle.  Chains are token lists in APPLICATION order as in tests/test_gpu_chains.py."""
+    block operator of weights, on the device and in the oracle.  Chains are token lists in APPLICATION order as in tests/test_gpu_chains.py.
+    data(tag, n): host arrays in place of the counter generator's U[0,1) streams -- tag ("A", i, j) the coefficients of block (i, j), ("w", k) the
+    k-th weights (nrow * n elements), ("c", k) the k-th domain diagonal (ncol * n elements)."""
 
-    def __init__(self, J, oracle, dt, nrow, ncol, n, mixed=False, seed=53):
+    def __init__(self, J, oracle, dt, nrow, ncol, n, mixed=False, seed=53, data=None):
         self.J, self.o, self.dt, self.nrow, self.ncol, self.n = J, oracle, dt, nrow, ncol, n
-        self.A, self.ora = _mixed_ops(J, oracle, dt, _grid_kinds(nrow, ncol, mixed), [n] * nrow, [n] * ncol, seed=seed)
+        self.A, self.ora = _mixed_ops(J, oracle, dt, _grid_kinds(nrow, ncol, mixed), [n] * nrow, [n] * ncol, seed=seed,
+                                      coeff=None if data is None else (lambda i, j, nr: data(("A", i, j), nr)))
         R, D = J.range(self.A), J.domain(self.A)
-        self.w = [J.rand(R, seed=seed + 1 + k, stream=0) for k in range(2)]
+        if data is None:
+            self.w = [J.rand(R, seed=seed + 1 + k, stream=0) for k in range(2)]
+            self.c = [J.rand(D, seed=seed + 5 + k, stream=0) for k in range(2)]
+        else:
+            self.w = [J.from_numpy(np.ascontiguousarray(data(("w", k), nrow * n), dtype=dt), R) for k in range(2)]
+            self.c = [J.from_numpy(np.ascontiguousarray(data(("c", k), ncol * n), dtype=dt), D) for k in range(2)]
         self.hw = [[b.copy() for b in np.split(w.to_numpy().ravel(order="F"), nrow)] for w in self.w]
-        self.c = [J.rand(D, seed=seed + 5 + k, stream=0) for k in range(2)]
         self.hc = [np.split(c.to_numpy().ravel(order="F").copy(), ncol) for c in self.c]
         self.W = [J.JopDiagonal(w) for w in self.w]
         self.M = [J.JopDiagonal(c) for c in self.c]
