@@ -419,6 +419,24 @@ int jh_chain_destroy(jh_chain *chain);
  * anything is touched: R and R^H together exceed 4 range-side stages (the caller keeps the chain-then-adjoint route), a vector not aligned like
  * its scalar, or the operator was pointed again since the row table was built while the library stream is capturing. */
 int jh_chain_bidiag_step(const jh_chain *fwd, jh_bvec *u, const jh_bvec *v, jh_bvec *w, double alpha, double beta, double *normsq);
+/* jh_chain_bidiag_step_range: the same step over the domain's elements [first_elem, first_elem + count) -- weighted LSQR / CGLS (the solvers over
+ * vec(L), src/Jets.jl:1138-1154, on the composite of 530-540) over a row partition, where w = L'u is summed over the ranks (1034-1057 on each
+ * rank's rows) and a finished range of w is all-reduced (jh_comm_allreduce_sum_range) under the next range's kernel.  For the packs of the range
+ * and every row i in order: t_i = R(a_i .* P(v)) ; u_i <- alpha*t_i + beta*u_i (beta == 0: u not read) ; w = Q(sum_i conj(a_i) .* R^H(u_i)).
+ * Touches those columns of every row of u and w[first_elem, first_elem + count), nothing else, with the values jh_chain_bidiag_step produces
+ * there: the bits where both walk the rows in one part (always with jh_tune_set("adj_split", 0)); u's bits always; tolerance parity for w where
+ * the many-small-rows split walk cuts the rows differently (each range is launched as a vector of its own length, like jh_chain_apply_range).
+ * *normsq = that range's share of ||u||^2 (fp64 per-workgroup partials folded in a fixed order; the call synchronises).  normsq NULL: no
+ * synchronisation -- the share is ADDED, in enqueue order, to the context's deferred accumulator (jh_normsq_reset before the first range,
+ * jh_normsq_read / jh_comm_allreduce_normsq after the last), as in jh_blockop_bidiag_step_range.  Bounds in elements (a complex element counts
+ * once) on 16-byte boundaries, except that the last range may end with the vector; count == 0 is a no-op.  Per range (3 + nw) N c s bytes for its
+ * c columns and no range-sized temporary, against (8 + 2 nw) N n s per step for the FORWARD chain into a temporary, the lincomb, the norm and the
+ * ranged ADJOINT chain.  Counter "last_adj_parts" is the call's.  JH_ERR_INVALID: not a FORWARD chain, vectors of the wrong length or aliased,
+ * bounds outside the vector or off the 16-byte grid.  JH_ERR_UNSUPPORTED before anything is touched: R and R^H together exceed 4 range-side
+ * stages, a vector not aligned like its scalar, a grid chain, or the operator was pointed again since the row table was built while the library
+ * stream is capturing. */
+int jh_chain_bidiag_step_range(const jh_chain *fwd, jh_bvec *u, const jh_bvec *v, jh_bvec *w, double alpha, double beta, int64_t first_elem, int64_t count,
+                               double *normsq);
 
 /* Fused solver updates (the two halves of an LSQR / CGLS iteration; callers: IterativeSolvers-style loops over
  * vec(A), src/Jets.jl:1138-1154).  d = alpha*(A m) + beta*d  /  m = alpha*(A' d) + beta*m  with real alpha, beta,

@@ -166,6 +166,7 @@ SYMBOLS = {
     "jh_chain_apply_range": (_int, [_vp, _vp, _vp, _int, _i64, _i64]),
     "jh_chain_destroy": (_int, [_vp]),
     "jh_chain_bidiag_step": (_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, _dblp]),
+    "jh_chain_bidiag_step_range": (_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, _i64, _i64, _dblp]),
     "jh_blockop_mul_axpby": (_int, [_vp, _vp, _vp, C.c_double, C.c_double, _dblp]),
     "jh_blockop_mul_adj_axpby": (_int, [_vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _dblp]),
     "jh_blockop_mul_scaled": (_int, [_vp, _vp, _vp, C.c_double, _int]),

@@ -8,7 +8,9 @@ For a device-native tall block operator the whole loop runs behind the C ABI (jh
 passes per iteration and no range-sized temporary -- ||A p||^2 = <p, A'A p> through the fused normal operator (N n s bytes),
 then r <- r - alpha A p, ||r||^2 and A'r in one pass of the Golub-Kahan step kernel (3 N n s).  Any other operator runs the
 textbook loop (q = A p kept in a range vector) over the same engines as LSQR: the two fused halves where they exist
-(jh_blockop_mul_axpby / jh_blockop_mul_adj_axpby), plain mul! otherwise; row-partitioned and team operators included.
+(jh_blockop_mul_axpby / jh_blockop_mul_adj_axpby), plain mul! otherwise; row-partitioned and team operators included.  A WEIGHTED shard or team
+(L = W o A, ...) under an exchange takes the two-pass form here too (cgls_core, `step_cgls`): <p, L'L p> through the ranged NORMAL chain, then the
+ranged one-pass chain step (jh_chain_bidiag_step_range) -- no range-sized temporary.
 """
 from __future__ import annotations
 
@@ -38,7 +40,13 @@ def cgls_core(eng, b, x0, damp, atol, btol, maxiter, overwrite_b=False, force_ma
     r = b if overwrite_b else eng.copy(eng.zeros_rng(), b)
     bnorm = eng.norm_rng(b)
     rnorm = eng.fwd(r, x, -1.0, 1.0) if x0 is not None else bnorm          # r = b - A x0
-    s, p, q = eng.zeros_dom(), eng.zeros_dom(), eng.zeros_rng()
+    # an engine with a one-pass step AND a `normal` hook that asks for it (`step_cgls`: a weighted shard or team, lsqr._ShardEngine / _TeamEngine)
+    # runs the two passes of jh_lsqr.hip's cgls_impl: delta = <p, A'A p> through the hook, then r <- r - alpha A p, ||r|| and A'r in one step --
+    # no q.  Should the step decline (before anything is touched), the textbook passes take over from that iteration on.
+    two_pass = bool(getattr(eng, "step_cgls", False))
+    s, p = eng.zeros_dom(), eng.zeros_dom()
+    q = None if two_pass else eng.zeros_rng()
+    y = eng.zeros_dom() if two_pass else None
     eng.adj(s, r, 1.0, 0.0)                                                 # s = A'r
     if damp:
         eng.lincomb(s, [1.0, -damp * damp], [s, x])
@@ -49,16 +57,27 @@ def cgls_core(eng, b, x0, damp, atol, btol, maxiter, overwrite_b=False, force_ma
     if gamma > 0:
         while itn < maxiter:
             itn += 1
-            qn = eng.fwd(q, p, 1.0, 0.0)                                     # q = A p, ||q||
-            delta = qn * qn + (damp * eng.norm_dom(p)) ** 2
+            if two_pass:
+                delta = eng.normal(y, p) + (damp * eng.norm_dom(p)) ** 2    # <p, A'A p> in one pass
+            else:
+                qn = eng.fwd(q, p, 1.0, 0.0)                                 # q = A p, ||q||
+                delta = qn * qn + (damp * eng.norm_dom(p)) ** 2
             if not (delta > 0 and math.isfinite(delta)):
                 istop, itn = 6, itn - 1
                 break
             alpha = gamma / delta
             eng.lincomb(x, [1.0, alpha], [x, p])
-            eng.lincomb(r, [1.0, -alpha], [r, q])
-            rnorm = eng.norm_rng(r)
-            eng.adj(s, r, 1.0, 0.0)                                         # s = A'r - damp^2 x
+            fused = eng.step(r, p, -alpha, 1.0) if two_pass else None       # r <- r - alpha A p ; ||r|| ; A'r
+            if fused is not None:
+                rnorm = fused[0]
+                eng.copy(s, fused[1])
+            else:
+                if two_pass:
+                    two_pass, q = False, eng.zeros_rng()
+                    eng.fwd(q, p, 1.0, 0.0)
+                eng.lincomb(r, [1.0, -alpha], [r, q])
+                rnorm = eng.norm_rng(r)
+                eng.adj(s, r, 1.0, 0.0)                                     # s = A'r - damp^2 x
             if damp:
                 eng.lincomb(s, [1.0, -damp * damp], [s, x])
             gamma_new = eng.norm_dom(s) ** 2

@@ -34,6 +34,7 @@ ENABLED = [True]        # tests / A-B timings: [False] sends every composite and
 STATS = {"chain_calls": 0, "sum_terms_fused": 0, "bcast_calls": 0,    # how often a fused run was applied (tests assert that the fused path is the one that ran)
          "chain_range_calls": 0,                                      # ... and how often one ran on an element range of the domain (rowpart's pipelined exchange)
          "chain_step_calls": 0, "chain_solve_calls": 0,               # the solvers on a FORWARD chain: one-pass steps (jh_chain_bidiag_step), whole native solves (jh_*_solve_chain)
+         "chain_step_range_calls": 0,                                 # one-pass steps on an element range (jh_chain_bidiag_step_range: weighted shards and teams; also in chain_range_calls)
          "grid_chain_calls": 0,                                       # fused runs through an N x (2 .. 4) grid (also counted in chain_calls / chain_solve_calls)
          "grid_step_calls": 0, "grid_solve_calls": 0}                 # the solvers on a bare grid: one-pass steps (jh_blockop_bidiag_step), native LSQR / CGLS solves
 
@@ -228,6 +229,17 @@ class ChainHandle:
         check(lib.jh_chain_apply_range(self._h, out.handle, x.handle, accumulate, int(first), int(count)))
         STATS["chain_range_calls"] += 1
         return out
+
+    def bidiag_step_range(self, u, v, w, alpha: float, beta: float, first: int, count: int, read_normsq: bool = False):
+        """The Golub-Kahan step of a FORWARD chain on the domain's elements [first, first + count) (jh_chain_bidiag_step_range): those columns of
+        every row of u, that range of w.  read_normsq: returns the range's share of ||u||^2 (synchronises); otherwise the share joins the
+        context's deferred accumulator (jh_normsq_reset / jh_normsq_read) and None is returned."""
+        out = C.c_double(0) if read_normsq else None
+        check(lib.jh_chain_bidiag_step_range(self._h, u.handle, v.handle, w.handle, float(alpha), float(beta), int(first), int(count),
+                                             C.byref(out) if read_normsq else None))
+        STATS["chain_range_calls"] += 1
+        STATS["chain_step_range_calls"] += 1
+        return out.value if read_normsq else None
 
     def close(self):
         if self._h is not None and self._h.value:

@@ -181,7 +181,7 @@ int tall_adj(const jh_blockop *op, void *out, const void *in, int mode, bool mix
 int fold_parts(int dtype, const void *parts, int64_t part_stride, int64_t nparts, void *out, int64_t s_begin, int64_t s_end);   // (scalars: a complex vector is 2n reals)
 int split_adjoint_tmp(const jh_blockop *op, void **tmp);
 // ---- jh_tall_step.hip
-int step_finish_normsq(int64_t nparts, double *normsq);   // fold ctx.part_dev[0 .. nparts) in a fixed order; normsq != NULL: read it back (synchronises)
+int step_finish_normsq(int64_t nparts, double *normsq, bool defer = false);   // fold ctx.part_dev[0 .. nparts) in a fixed order; normsq != NULL: read it back (synchronises); NULL and defer: add it to the deferred accumulator (jh_normsq_reset / jh_normsq_read)
 // ---- jh_general.hip
 int general_fwd(const jh_blockop *op, void *d, const void *m, int fmode = 0);
 int general_adj(const jh_blockop *op, void *m, const void *d);

@@ -8,7 +8,8 @@ namespace jhb {
 // (ca: another program over the handle's rows and streams -- a FORWARD chain's derived ADJOINT / NORMAL program; NULL: the handle's own)
 int chain_launch_adjoint(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem, const ChainArgs *ca = nullptr);   // jh_tall_chain_adj.hip
 int chain_launch_normal(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem, const ChainArgs *ca = nullptr);    // jh_tall_chain_nrm.hip
-int chain_launch_step(const jh_chain *ch, const ChainArgs &ca, void *u, const void *v, void *w, double alpha, double beta, double *normsq);   // jh_tall_chain_step.hip
+int chain_launch_step(const jh_chain *ch, const ChainArgs &ca, void *u, const void *v, void *w, double alpha, double beta, double *normsq,
+                      int64_t first_elem, int64_t end_elem, bool defer);                                      // jh_tall_chain_step.hip
 bool grid_chain_ok(const jh_blockop *op);                                                                     // jh_grid_chain.hip
 bool grid_chain_vectors_ok(const jh_blockop *op, const void *a, const void *b);
 int grid_chain_launch(const jh_chain *ch, int prog, int type, void *out, const void *in, int accumulate);   // prog: 0 own, 1 / 2 the derived ADJOINT / NORMAL
@@ -317,7 +318,39 @@ int jh_chain_bidiag_step(const jh_chain *fwd, jh_bvec *u, const jh_bvec *v, jh_b
     if (!jhb::tall_unaligned_ok(op, u->data, v->data) || !jhb::tall_unaligned_ok(op, nullptr, w->data))
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step: a vector or coefficient array is not aligned like its scalar");
     JH_TRY(fwd_ready(fwd, "jh_chain_bidiag_step"));
-    return jhb::chain_launch_step(fwd, fwd->step_args, u->data, v->data, w->data, alpha, beta, normsq);
+    return jhb::chain_launch_step(fwd, fwd->step_args, u->data, v->data, w->data, alpha, beta, normsq, 0, w->length, false);
+}
+
+// The step over the domain's elements [first_elem, first_elem + count): those columns of every row of u, that range of w, that range's share of ||u||^2
+// -- what a host pipelining the exchange of w range by range against the kernels runs (weighted LSQR / CGLS over a row partition: src/Jets.jl:530-540
+// over 1034-1057 summed across the ranks, the solvers over vec(L) 1138-1154).  The checks of jh_chain_bidiag_step and the bounds of
+// jh_chain_apply_range, all before anything is touched.
+int jh_chain_bidiag_step_range(const jh_chain *fwd, jh_bvec *u, const jh_bvec *v, jh_bvec *w, double alpha, double beta, int64_t first_elem, int64_t count,
+                               double *normsq)
+{
+    JH_REQUIRE(fwd && u && v && w, "jh_chain_bidiag_step_range: null argument");
+    JH_REQUIRE(fwd->type == JH_CHAIN_FORWARD, "jh_chain_bidiag_step_range: needs a FORWARD chain (got type %d)", fwd->type);
+    if (fwd->ncol > 1) return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step_range: a grid chain has no one-pass step (run the FORWARD chain, then the ADJOINT)");
+    if (!fwd->nrm_ok)
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step_range: R and R^H need more than %d range-side stages", JH_CHAIN_MAX_STAGES);
+    const jh_blockop *op = fwd->op;
+    JH_TRY(jh_enter(op, u, v, w));
+    const int64_t nrange = op->row_off[(size_t)op->nrow], ndom = op->col_off[(size_t)op->ncol];
+    JH_REQUIRE(u->dtype == op->dtype && v->dtype == op->dtype && w->dtype == op->dtype, "jh_chain_bidiag_step_range: dtype mismatch");
+    JH_REQUIRE(u->length == nrange && v->length == ndom && w->length == ndom,
+               "jh_chain_bidiag_step_range: u must be a range vector, v and w domain vectors of the operator");
+    JH_REQUIRE(w->data != v->data && u->data != v->data && u->data != w->data, "jh_chain_bidiag_step_range: u, v and w must be three vectors");
+    JH_REQUIRE(first_elem >= 0 && count >= 0 && first_elem <= ndom - count,
+               "jh_chain_bidiag_step_range: elements [%lld, %lld) outside the domain vector (%lld elements)", (long long)first_elem,
+               (long long)(first_elem + count), (long long)ndom);
+    const int64_t es = (int64_t)jh_dtype_size(op->dtype);
+    JH_REQUIRE((first_elem * es) % 16 == 0 && ((count * es) % 16 == 0 || first_elem + count == ndom),
+               "jh_chain_bidiag_step_range: range boundaries must be 16-byte aligned (the last range may end with the vector)");
+    if (!jhb::tall_unaligned_ok(op, u->data, v->data) || !jhb::tall_unaligned_ok(op, nullptr, w->data))
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step_range: a vector or coefficient array is not aligned like its scalar");
+    if (count == 0) return JH_OK;
+    JH_TRY(fwd_ready(fwd, "jh_chain_bidiag_step_range"));
+    return jhb::chain_launch_step(fwd, fwd->step_args, u->data, v->data, w->data, alpha, beta, normsq, first_elem, first_elem + count, true);
 }
 
 }  // extern "C"

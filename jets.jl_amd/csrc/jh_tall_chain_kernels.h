@@ -266,6 +266,9 @@ __global__ __launch_bounds__(BLK) void k_chain_fwd(const jh_dev_block *__restric
 // MODE 2 (the Golub-Kahan step of a FORWARD chain, jh_chain_bidiag_step): MODE 1 with R^H after R (mid_step) and the update of u between them --
 //   t_i = R(a_i .* P(in)) ;  u_i <- alpha t_i + beta u_i (beta == 0: u not read) ;  out = Q( sum_i conj(a_i) .* R^H(u_i) ) ;  partial ||u||^2
 // u_i is written by the lane that owns the pack (st_pack), so the rows' updates need no other lane; ||u||^2 is one fp64 partial per workgroup.
+// Over a range [s_begin, s_end) of the domain (jh_chain_bidiag_step_range) the step touches those columns of every row of u, that range of `out` and
+// counts that range's share of ||u||^2: every scalar of u and of the ordered row sum depends on its own column alone, so the ranges together have
+// the whole-vector step's bits.
 // The ordered walk of k_tall_diag_adj (jh_tall.hip): a thread owns U packs of the domain and walks all rows in order, DEPTH rows' loads in flight, the
 // next DEPTH rows' table records already requested.
 template <typename S, int E, int NS, int U, int DEPTH, bool NT, int MODE, int BLK, int NW>
@@ -519,12 +522,14 @@ int launch_chain_fwd(const jh_chain *ch, void *d, const void *m, int64_t n_scala
 // whole vector of its length -- shape, grid and split-walk parts from the RANGE's pack count, as launch_tall_adj_u does -- so where the whole-vector
 // call and a range both walk the rows in one part they have the same bits (every scalar is its own ordered row sum); where the part counts differ
 // (many rows of small blocks: pick_adj_parts) the fold adds different partial sums -- tolerance parity, DESIGN.md section 3.  The nontemporal choice
-// stays the whole application's: a range's coefficients come back one application later, after every other range's.
+// stays the whole application's: a range's coefficients come back one application later, after every other range's -- the ranged step's too (its
+// working set between two visits of a range is the whole step's: every range's coefficients and columns of u).
 // The step's extra operands (MODE 2): u, its coefficients and where ||u||^2 goes (NULL: not read back)
 struct ChainStep {
     void *u = nullptr;
     double alpha = 1.0, beta = 0.0;
     double *normsq = nullptr;
+    bool defer = false;                      // a ranged step (jh_chain_bidiag_step_range) with normsq NULL: its share joins the deferred accumulator
 };
 
 // `ca`: the handle's own program, or one derived from it (the ADJOINT / NORMAL / step programs of a FORWARD chain: jh_tall_chain.hip)
@@ -618,7 +623,7 @@ int launch_chain_adj(const jh_chain *ch, const ChainArgs &ca, void *out, const v
     }
     if (MODE == 2) {
         c.last_step_parts = gx * parts;
-        return jhb::step_finish_normsq(gx * parts, step->normsq);
+        return jhb::step_finish_normsq(gx * parts, step->normsq, step->defer);
     }
     return JH_OK;
 }

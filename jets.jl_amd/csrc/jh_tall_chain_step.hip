@@ -3,20 +3,26 @@
 #include "jh_tall_chain_kernels.h"
 
 namespace jhb {
-int chain_launch_step(const jh_chain *ch, const ChainArgs &ca, void *u, const void *v, void *w, double alpha, double beta, double *normsq)
+// the domain's elements [first_elem, end_elem): the whole vector (jh_chain_bidiag_step) or one exchange range (jh_chain_bidiag_step_range) -- those
+// columns of every row of u, that range of w, that range's share of ||u||^2.  The bounds are kernel ARGUMENTS (s_begin, s_end of k_chain_adj, as for the
+// ranged ADJOINT / NORMAL chains): the ranged step runs the whole-vector step's instantiations.  defer: normsq NULL adds the share to the deferred
+// accumulator (jh_normsq_reset / jh_normsq_read) instead of dropping it.
+int chain_launch_step(const jh_chain *ch, const ChainArgs &ca, void *u, const void *v, void *w, double alpha, double beta, double *normsq,
+                      int64_t first_elem, int64_t end_elem, bool defer)
 {
     const jh_blockop *op = ch->op;
-    const int64_t n = op->row_len[0];
+    const int64_t n = op->row_len[0], lo = first_elem, hi = end_elem;
     ChainStep st;
     st.u = u;
     st.alpha = alpha;
     st.beta = beta;
     st.normsq = normsq;
+    st.defer = defer;
     switch (op->dtype) {
-    case JH_F32: return launch_chain_adj<float, 1, 4, 2>(ch, ca, w, v, n, 0, 0, n, &st);
-    case JH_F64: return launch_chain_adj<double, 1, 2, 2>(ch, ca, w, v, n, 0, 0, n, &st);
-    case JH_C32: return launch_chain_adj<float, 2, 4, 2>(ch, ca, w, v, n * 2, 0, 0, n * 2, &st);
-    case JH_C64: return launch_chain_adj<double, 2, 2, 2>(ch, ca, w, v, n * 2, 0, 0, n * 2, &st);
+    case JH_F32: return launch_chain_adj<float, 1, 4, 2>(ch, ca, w, v, n, 0, lo, hi, &st);
+    case JH_F64: return launch_chain_adj<double, 1, 2, 2>(ch, ca, w, v, n, 0, lo, hi, &st);
+    case JH_C32: return launch_chain_adj<float, 2, 4, 2>(ch, ca, w, v, n * 2, 0, lo * 2, hi * 2, &st);
+    case JH_C64: return launch_chain_adj<double, 2, 2, 2>(ch, ca, w, v, n * 2, 0, lo * 2, hi * 2, &st);
     }
     return jh_fail(JH_ERR_INVALID, "chain_launch_step: unknown dtype %d", op->dtype);
 }

@@ -1010,7 +1010,7 @@ int launch_bidiag(const jh_blockop *op, void *u, const void *v, void *w, int64_t
 }  // namespace
 
 namespace jhb {
-int step_finish_normsq(int64_t nparts, double *normsq) { return finish_normsq(nparts, normsq); }
+int step_finish_normsq(int64_t nparts, double *normsq, bool defer) { return finish_normsq(nparts, normsq, defer); }
 }  // namespace jhb
 
 // into how many row ranges the one-pass step over the whole domain cuts this operator (1: one plain launch -- what the graph-replayed

@@ -75,7 +75,7 @@ class _Engine:
         self.fused_step = os.environ.get("JETS_LSQR_FUSED_STEP", "1") != "0"   # one pass per iteration (jh_blockop_bidiag_step)
         # a composite that is ONE fused FORWARD chain (W o A, W o A o M, a * (W o A)): its one-pass step, its native solves and cgnr_core's
         # NORMAL-chain hook (chains.SolverChains; JETS_CHAIN_STEP=0: the chain into a range temporary, then the ADJOINT chain).  One GPU only:
-        # the row-partitioned and team engines keep their routes.
+        # the row-partitioned and team engines take the ranged form of the step (rowpart: jh_chain_bidiag_step_range).
         self.chains = None
         self._tmp_q = None
         # a bare N x (2 .. 4) grid (one GPU): its own one-pass step and the native LSQR / CGLS loops on it (jh_grid_step.hip); None when the operator is
@@ -238,6 +238,9 @@ class _ShardEngine(_Engine):
         self.force_collective = os.environ.get("BENCH_FORCE_DIST", "0") == "1"   # run the exchange even with one rank (validation)
         if getattr(shard, "fused_normal", False):
             self.normal = self._normal                   # a weighted shard: cgnr_core applies L'L as one NORMAL chain + a pipelined exchange
+        # a weighted shard under an exchange: the one-pass chain step range by range (rowpart: jh_chain_bidiag_step_range), no range temporary --
+        # LSQR every iteration, the warm start, CGLS's second pass (cgls.cgls_core).  JETS_CHAIN_STEP=0: the chain into a range temporary, as before.
+        self.chain_step = bool(getattr(shard, "chain_step", False)) and (shard.comm.world > 1 or self.force_collective)
 
     def _normal(self, y, p) -> float:
         """y = L'L p summed over the ranks (rowpart: normal_mul_, one fused pass + the ranged all-reduces); returns <p, y>, taken on the
@@ -249,16 +252,26 @@ class _ShardEngine(_Engine):
     def norm_rng(self, x) -> float:
         return self.shard.norm_range(x, 2)
 
+    @property
+    def step_cgls(self) -> bool:
+        """cgls_core takes its two-pass form: <p, L'L p> through `normal`, then r <- r - alpha L p, ||r|| and L'r in one ranged chain step."""
+        return self.chain_step and self.fused_step and getattr(self, "normal", None) is not None
+
     def fwd(self, u, v, alpha, beta) -> float:
+        if self.chain_step and self.fused_step:          # a chain has no forward-with-axpby: one step into the scratch domain vector (the warm start)
+            r = self.step(u, v, alpha, beta)
+            if r is not None:
+                return r[0]
         return math.sqrt(self.shard.comm.all_reduce_scalars([self._fwd_local(u, v, alpha, beta)], "sum")[0])
 
     def step(self, u, v, alpha, beta):
-        if self.native is not None and self.fused_step:  # pipelined: all-reduce of a finished chunk of A'u under the next chunk's kernel
+        if (self.native is not None or self.chain_step) and self.fused_step:  # pipelined: all-reduce of a finished chunk of A'u under the next chunk's kernel
             if self._tmp_d is None:
                 self._tmp_d = zeros(_j.domain(self.A))
             nrm2 = self.shard.bidiag_step_(u, v, self._tmp_d, alpha, beta, force_collective=self.force_collective)
             if nrm2 is not None:
                 return math.sqrt(nrm2), self._tmp_d
+            self.chain_step = False                      # (a weighted shard whose step the library declined: the two halves from here on)
         r = self._step_local(u, v, alpha, beta)          # this rank's rows: local ||u||^2 and local A'u
         if r is None:
             return None
@@ -292,6 +305,23 @@ class _TeamEngine:
         self._tmp_d = None
         self._engines = [_Engine(A) for A in T.local_ops]     # per member: the fused local halves
         self.fused_step = os.environ.get("JETS_LSQR_FUSED_STEP", "1") != "0"
+        # members that are weighted chains (W_k o A_k, ...): the ranged chain step and the ranged NORMAL chain of rowpart.TeamOp
+        self.chain_step = bool(getattr(T, "chain_step", False))
+        if getattr(T, "fused_normal", False):
+            self.normal = self._normal
+
+    @property
+    def step_cgls(self) -> bool:
+        return self.chain_step and self.fused_step and getattr(self, "normal", None) is not None
+
+    def _normal(self, y, p) -> float:
+        """y = L'L p summed over the members (TeamOp.normal_mul_); returns <p, y> on member 0's replica."""
+        self.T.normal_mul_(y, p)
+        from . import device as _device
+
+        _device.context_use(self.team.contexts[0])
+        v = dot(p[0], y[0])
+        return float(getattr(v, "real", v))
 
     def native_solver(self, solver: str):
         """jh_*_solve_team: the whole loop over the team behind ONE call (what the Julia binding uses); None when a member has no native
@@ -329,6 +359,10 @@ class _TeamEngine:
         return math.sqrt(builtins.sum(float(norm(x[k])) ** 2 for k, _ in self.team.each()))
 
     def fwd(self, u, v, alpha, beta) -> float:
+        if self.chain_step and self.fused_step:               # weighted members: one ranged step into the scratch domain vectors (the warm start)
+            r = self.step(u, v, alpha, beta)
+            if r is not None:
+                return r[0]
         return math.sqrt(builtins.sum(self._engines[k]._fwd_local(u[k], v[k], alpha, beta) for k, _ in self.team.each()))
 
     def step(self, u, v, alpha, beta):
@@ -337,7 +371,10 @@ class _TeamEngine:
         if self._tmp_d is None:
             self._tmp_d = self.zeros_dom()
         nrm2 = self.T.bidiag_step_(u, v, self._tmp_d, alpha, beta)
-        return None if nrm2 is None else (math.sqrt(nrm2), self._tmp_d)
+        if nrm2 is None:
+            self.chain_step = False
+            return None
+        return math.sqrt(nrm2), self._tmp_d
 
     def adj(self, v, u, alpha, beta) -> float:
         if self._tmp_d is None:

@@ -167,6 +167,11 @@ class RowPartitionedOp:
         """normal_mul_ needs no range temporary: a weighted shard (L = W_loc o A_loc, ...) applies L'L as one fused NORMAL chain."""
         return self._local_normal is not None
 
+    @property
+    def chain_step(self) -> bool:
+        """bidiag_step_ runs a weighted shard's one-pass chain step range by range (jh_chain_bidiag_step_range): no range temporary."""
+        return self._chains is not None and self._chains.has_step and self._pipelined_step is not None
+
     def close(self):
         """Release the chain handles of a weighted shard (the operator itself stays the caller's)."""
         if self._chains is not None:
@@ -193,7 +198,8 @@ class RowPartitionedOp:
     def bidiag_step_(self, u_local, v, w, alpha: float, beta: float, force_collective: bool = False):
         """u_local <- alpha*(A_local v) + beta*u_local ; w <- sum over ALL ranks of A_local' u_local, the all-reduce of a
         finished chunk of w overlapping the kernel of the next.  Returns the GLOBAL ||u||^2, or None when the local
-        operator has no ranged one-pass kernel (the caller then runs the step in one piece)."""
+        operator has no ranged one-pass kernel (the caller then runs the step in one piece).  A weighted shard (L = W_loc o A_loc, ...) runs
+        its FORWARD chain's step range by range (jh_chain_bidiag_step_range) the same way."""
         if self._pipelined_step is None or not (self.comm.world > 1 or force_collective):
             return None
         return self._pipelined_step(u_local, v, w, alpha, beta)
@@ -230,23 +236,29 @@ class _ShardChains:
     """The fused chains of a WEIGHTED shard: a local operator L that the chain planner (chains.py) turns into one run around the shard's
     tall operator -- W_loc o A_loc (W_loc = JopDiagonal of this rank's rows of the weights), a block-diagonal @blockop of weights o A_loc,
     W o A o M, a * (W o A).  adjoint(L) is one ADJOINT chain, adjoint(L) o L one NORMAL chain (W' and W read one coefficient stream:
-    jh_chain_create's dedupe).  Planned here once; the handles live in this object's cache until close().  A bare block operator is not
+    jh_chain_create's dedupe), L itself one FORWARD chain whose Golub-Kahan step runs range by range (jh_chain_bidiag_step_range: LSQR / CGLS
+    on the shard; JETS_CHAIN_STEP=0 keeps the chain into a range temporary, as chains.SolverChains does on one GPU).  Planned here once; the handles live in this object's cache until close().  A bare block operator is not
     weighted: plain shards keep their routes (jh_blockop_*_range)."""
 
     def __init__(self, L):
+        import os
+
         from . import chains as _chn
         from . import jetblock as _blk
         from .jets import JopLn, JopAdjoint, adjoint, compose, jops_comp
 
         self._chn = _chn
         self.cache = _chn.ChainCache()
-        self._adj = self._nrm = self._nrm_op = None
+        self._adj = self._nrm = self._nrm_op = self._fwd = None
         if isinstance(L, (JopLn, JopAdjoint)) and not _blk.isblockop(L) and len(jops_comp(L)) >= 2:
             self._nrm_op = compose(adjoint(L), L)
             self._adj = _chn.stages_of(adjoint(L))
             self._nrm = _chn.stages_of(self._nrm_op)
+            if os.environ.get("JETS_CHAIN_STEP", "1") != "0":
+                self._fwd = _chn.stages_of(L)
         self.has_adj = self._adj is not None and _chn.one_run(self._adj, self.cache, "rowpart_adj", _chn.CHAIN_ADJOINT, make=False, grid=False) is not None
         self.has_normal = self._nrm is not None and _chn.one_run(self._nrm, self.cache, "rowpart_normal", _chn.CHAIN_NORMAL, make=False, grid=False) is not None
+        self.has_step = self._fwd is not None and _chn.one_run(self._fwd, self.cache, "rowpart_fwd", _chn.CHAIN_FORWARD, make=False, grid=False) is not None
 
     def adjoint(self):
         """The ChainHandle of adjoint(L), or None (not one run; the library declined)."""
@@ -254,6 +266,10 @@ class _ShardChains:
 
     def normal(self):
         return self._chn.one_run(self._nrm, self.cache, "rowpart_normal", self._chn.CHAIN_NORMAL) if self.has_normal else None
+
+    def step(self):
+        """The FORWARD ChainHandle of L (its ranged Golub-Kahan step: ChainHandle.bidiag_step_range), or None."""
+        return self._chn.one_run(self._fwd, self.cache, "rowpart_fwd", self._chn.CHAIN_FORWARD, grid=False) if self.has_step else None
 
     def local_normal(self, y, L, m):
         """y = L'L m on this rank's rows: the whole-vector NORMAL chain (the stage-by-stage chain when the library declines it)."""
@@ -437,10 +453,17 @@ def _pipelined_routes(xch, local_op, sc) -> dict:
         """jh_blockop_bidiag_step in `nchunks` element ranges, enqueued back to back: every range adds its share of ||u||^2 to a device-side
         accumulator (jh_normsq_reset / normsq == NULL), so the host synchronises ONCE per step, after the last range (xch.normsq), while the
         all-reduces of the finished ranges of w run under the later kernels.  Returns the GLOBAL ||u||^2, or None when the operator has no
-        ranged one-pass kernel."""
+        ranged one-pass kernel.  A weighted shard: the same shape over its FORWARD chain's ranged step (jh_chain_bidiag_step_range)."""
         nat = native_of(local_op)
         if nat is None:
-            return None
+            h = sc.step() if nchunks > 1 and xch.ready() and sc.has_step else None
+            if h is None:
+                return None
+            check(lib.jh_normsq_reset())
+            r = _pipelined(xch, w, nchunks, lambda lo, cnt: h.bidiag_step_range(u, v, w, alpha, beta, lo, cnt), finish=xch.normsq)
+            if r is None:                                     # the library declined before anything was touched (R + R^H above four stages): for good
+                sc.has_step = False
+            return r
         check(lib.jh_normsq_reset())
         return _pipelined(xch, w, nchunks, lambda lo, cnt: check(lib.jh_blockop_bidiag_step_range(
             nat.handle, u.handle, v.handle, w.handle, float(alpha), float(beta), lo, cnt, None)), finish=xch.normsq)
@@ -577,6 +600,30 @@ class TeamOp:
                 jt = A.jet
                 nat = _blk._native_op(jt.s.get("_native"), jt.s["ops"], jt.rng.eltype())
             self._natives.append(nat)
+        # members whose local operators are WEIGHTED chains (W_k o A_k, ...: _ShardChains): the one-pass step and the normal operator range by
+        # range through each member's own chain handles, which live in that member's context (built on first use there, released by close())
+        self._chains = [None if nat is not None else _ShardChains(A) for nat, A in zip(self._natives, self.local_ops)]
+
+    @property
+    def chain_step(self) -> bool:
+        """Every member is a weighted chain with a ranged one-pass step (jh_chain_bidiag_step_range)."""
+        return all(sc is not None and sc.has_step for sc in self._chains)
+
+    @property
+    def fused_normal(self) -> bool:
+        """Every member is a weighted chain whose normal operator is one NORMAL chain (jh_chain_apply_range): normal_mul_ needs no `tmp`."""
+        return all(sc is not None and sc.has_normal for sc in self._chains)
+
+    def _member_handles(self, which: str):
+        """Every member's chain handle (`step` / `normal` of its _ShardChains), each built in its own context; None when one is missing."""
+        hs = [getattr(self._chains[k], which)() for k, _ in self.team.each()]
+        return None if any(h is None for h in hs) else hs
+
+    def close(self):
+        """Release the members' chain handles, each in its member's context (the operators stay the caller's)."""
+        for k, _ in self.team.each():
+            if self._chains[k] is not None:
+                self._chains[k].close()
 
     def domain(self):
         from .jets import domain
@@ -620,11 +667,12 @@ class TeamOp:
             mul_(d[k], self.local_ops[k], m[k])
         return d
 
-    def _ranged(self, m: TeamVec, enqueue_range) -> bool:
-        """For every range of the domain: every member's kernel for it, then the members' all-reduces of it in one group."""
+    def _ranged(self, m: TeamVec, enqueue_range, native: bool = True) -> bool:
+        """For every range of the domain: every member's kernel for it, then the members' all-reduces of it in one group.  native=False: the
+        kernels are the members' chains' (weighted members), not their block operators'."""
         from ._ffi import lib, check
 
-        if any(n is None for n in self._natives):
+        if native and any(n is None for n in self._natives):
             return False
         for lo, cnt in _chunk_bounds(m[0].length(), self.nchunks):
             for k, _ in self.team.each():
@@ -657,9 +705,15 @@ class TeamOp:
 
     def normal_mul_(self, y: TeamVec, m: TeamVec, tmp: TeamVec | None = None) -> TeamVec:
         """y = (A'A) m on every member's replica: the members' fused A_k'A_k m range by range, each range summed over the team under
-        the next range's kernels; forward then adjoint through `tmp` (a range-side TeamVec) for operators without the fused kernel."""
+        the next range's kernels; forward then adjoint through `tmp` (a range-side TeamVec) for operators without the fused kernel.  Members that
+        are weighted chains (W_k o A_k, ...) apply L_k'L_k as one NORMAL chain per range (jh_chain_apply_range) and need no `tmp`."""
         from ._ffi import lib, check, JetsHipError
 
+        if self.fused_normal:                                  # weighted members: L_k'L_k m as ONE NORMAL chain per member and range
+            hs = self._member_handles("normal")
+            if hs is not None:
+                self._ranged(y, lambda k, lo, cnt: hs[k].apply_range(y[k], m[k], lo, cnt, 0), native=False)
+                return y
         if self.one_call and self._team_call(lib.jh_team_normal_mul, y, m, self.nchunks):
             return y
         try:
@@ -673,22 +727,33 @@ class TeamOp:
         return self.mul_adj_(y, self.mul_(tmp, m))
 
     def bidiag_step_(self, u: TeamVec, v: TeamVec, w: TeamVec, alpha: float, beta: float):
-        """One Golub-Kahan step on every member (jh_blockop_bidiag_step_range per range) with the ranged exchange of w;
+        """One Golub-Kahan step on every member (jh_blockop_bidiag_step_range per range; weighted members: jh_chain_bidiag_step_range) with the ranged exchange of w;
         returns the GLOBAL ||u||^2 -- the host adds the members' deferred accumulators -- or None without a ranged kernel."""
         import ctypes as C
 
         from ._ffi import lib, check, JetsHipError
 
-        if any(n is None for n in self._natives):
+        hs = None
+        if self.chain_step:                                    # weighted members: jh_chain_bidiag_step_range per member and range
+            hs = self._member_handles("step")
+            if hs is None:
+                return None
+        elif any(n is None for n in self._natives):
             return None
         for _ in self.team.each():
             check(lib.jh_normsq_reset())
         try:
-            self._ranged(w, lambda k, lo, cnt: check(lib.jh_blockop_bidiag_step_range(
-                self._natives[k].handle, u[k].handle, v[k].handle, w[k].handle, float(alpha), float(beta), lo, cnt, None)))
+            if hs is not None:
+                self._ranged(w, lambda k, lo, cnt: hs[k].bidiag_step_range(u[k], v[k], w[k], alpha, beta, lo, cnt), native=False)
+            else:
+                self._ranged(w, lambda k, lo, cnt: check(lib.jh_blockop_bidiag_step_range(
+                    self._natives[k].handle, u[k].handle, v[k].handle, w[k].handle, float(alpha), float(beta), lo, cnt, None)))
         except JetsHipError as e:
-            if e.status != 4:
+            if e.status != 4:                                  # JH_ERR_UNSUPPORTED comes before anything is touched (member 0, the first range)
                 raise
+            if hs is not None:
+                for sc in self._chains:
+                    sc.has_step = False
             return None
         total = 0.0
         out = C.c_double(0)

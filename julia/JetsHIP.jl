@@ -1047,6 +1047,23 @@ function bidiag_step!(u::BlockArray{T,<:HipArray{T}}, w::HipArray{T}, chain::Ptr
                 chain, handle(u), handle(v), handle(w), alpha, beta, nrm2))
     sqrt(nrm2[])
 end
+# ... and over the domain's elements [first_elem, first_elem + count) (0-based, on 16-byte bounds; the last range may end with the vector): those columns
+# of every row of u, that range of w (jh_chain_bidiag_step_range) -- what a host that pipelines the exchange of w over a row partition runs range by range
+# (530-540 over 1034-1057 summed across the ranks).  deferred = true: no synchronisation, the range's share of ||u||^2 joins the context's accumulator
+# (jh_normsq_reset before the first range, jh_normsq_read after the last) and `nothing` is returned; else the share itself (not its square root: shares add).
+function bidiag_step_range!(u::BlockArray{T,<:HipArray{T}}, w::HipArray{T}, chain::Ptr{Cvoid}, v::HipArray{T}, alpha::Real, beta::Real,
+                            first_elem::Integer, count::Integer; deferred::Bool=false) where {T}
+    chain == C_NULL && error("bidiag_step_range!: needs a planned FORWARD chain through a tall operator (_plan_chain(L, T; grid=false))")
+    if deferred
+        check(ccall((:jh_chain_bidiag_step_range, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Int64, Int64, Ptr{Cdouble}),
+                    chain, handle(u), handle(v), handle(w), alpha, beta, first_elem, count, C_NULL))
+        return nothing
+    end
+    share = Ref{Cdouble}()
+    check(ccall((:jh_chain_bidiag_step_range, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Int64, Int64, Ref{Cdouble}),
+                chain, handle(u), handle(v), handle(w), alpha, beta, first_elem, count, share))
+    share[]
+end
 
 # the FORWARD chain handle of a composite that plans to ONE fused run R ∘ A ∘ P (W ∘ A, W ∘ A ∘ M, a * (W ∘ A)), or C_NULL: what the solvers below take
 # in place of a tall block operator (jh_*_solve_chain)
