@@ -375,8 +375,17 @@ int jh_blocksum_mul_adj_typed(int nterms, const jh_blockop *const *ops, const do
  * stage-by-stage composite, every coefficient read once.  jh_chain_apply and jh_chain_destroy work unchanged, accumulate included; the many-small-
  * rows split walk sums in parts as above.  jh_chain_apply_range and jh_chain_bidiag_step on a grid chain return JH_ERR_UNSUPPORTED before touching
  * anything (no ranged form, no one-pass step), and so do jh_lsqr_solve_chain and jh_cgls_solve_chain on a grid FORWARD chain (keep the two-pass
- * loops: two fused grid chains); jh_cgnr_solve_chain runs on the derived ADJOINT and NORMAL programs.  Counter "last_grid_chain_shape": bit 0
+ * loops: two fused grid chains) -- unless knob "grid_chain_step" = 1: GRID CHAIN STEP below; jh_cgnr_solve_chain runs on the derived ADJOINT and
+ * NORMAL programs.  Counter "last_grid_chain_shape": bit 0
  * nontemporal loads, bit 1 rows in parts, bit 2 the stages after A' run on the folded parts.  Knob "grid_chain" = 0: grids are declined as before.
+ * GRID CHAIN STEP (knob "grid_chain_step" = 1; the default is 0): jh_chain_bidiag_step takes a FORWARD grid chain L = R o A o P in ONE pass --
+ *   t_i = R( ((0 + a_i1 .* P(v)_1) + a_i2 .* P(v)_2) + ... ) ;  u_i <- alpha*t_i + beta*u_i ;  w_k = Q( ((0 + conj(a_1k) .* R^H(u_1)) + ...) ) ;  ||u||^2
+ * with the bits of the FORWARD grid chain into a temporary, the lincomb and the derived ADJOINT grid chain (the many-small-rows split walk sums w
+ * in parts: tolerance parity, adj_split = 0 the bits), (N K + (nw + 2) N + 2 K) n s bytes against (2 N K + (2 nw + 6) N + 2 K) n s -- and
+ * jh_lsqr_solve_chain / jh_cgls_solve_chain iterate on it, host-driven (the warm start is one step into a scratch domain vector; CGLS's first pass
+ * is the derived NORMAL grid chain).  The checks of jh_chain_bidiag_step hold unchanged, all before anything is touched.  Counter
+ * "last_grid_chain_step_shape": bit 0 nontemporal loads, bit 1 rows in parts.  jh_chain_apply_range and jh_chain_bidiag_step_range decline grid
+ * chains under either setting.
  * JH_ERR_UNSUPPORTED (take the stage-by-stage chain): operators that are not tall or such a grid / elementwise / equal rows, one-row operators,
  * dense or nonlinear grid children, K > 4, arrays not aligned like their scalar. */
 typedef struct jh_chain jh_chain;
@@ -633,7 +642,7 @@ int jh_team_normal_mul(int n, const jh_blockop *const *ops, jh_bvec *const *ys, 
  * aligned loads of diagonals laid out like the range vector: -1 rows of 64 KiB or more, 0 never, 1 always; same bits), "tall_f" (F(m) of a tall nonlinear operator of elementwise children -- jh_blockop_f -- on the tall tiling: 1 yes, 0 the
  * general kernels; same bits), "dense_list_shared" (round 6: the rows pass of y = B x for DENSE children whose columns are off the 16-byte grid numbers its
  * chunks XCD by XCD and loads temporally, so the 128-byte line two neighbouring rows share is fetched from HBM once: 1 yes, 0 round 5's pass; same bits),
- * "dense_list_rl_min" (log2 of the fewest row lanes per workgroup of that pass, 0: automatic), "red_blocks_wave" (round 6: jh_norm_blocks / jh_dot_blocks of many blocks of at most 16 KiB with a wave per block in one launch: 1 yes, 0 a workgroup per block + the fold; within the reductions' tolerance of each other), "adj_bare_chain" (round 6: jh_blockop_mul_adj and jh_blockop_normal_mul of a tall operator with rows of several kinds, or rows off the 16-byte grid, of up to 4 MiB on the chain kernels with empty stage lists -- packed row records --: 1 yes, 0 the MIXED tall kernel; same bits unless the split walk's part count changes), "adj_thin_mixed" (round 6: the adjoint of a tall operator with rows of several kinds on thin workgroups when fat ones would leave CUs idle -- rows of 1-8 MiB --: 1 yes, 0 round 5's shapes; same bits unless the split walk's part count changes), "grid_normal" (round 6: jh_blockop_normal_mul on N x (2 .. 4) grids of equal elementwise blocks -- diagonals, zero / identity / scalar blocks -- in one pass: 1 yes, 2 grids of plain diagonals only, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_step" (jh_blockop_bidiag_step, jh_lsqr_solve and jh_cgls_solve on N x (2 .. 4) grids of equal elementwise blocks in one pass per step: 1 yes, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_chain" (jh_chain_create on N x (2 .. 4) grids of equal elementwise blocks -- fused chains A' o W o A, (W o A)', W o A through a multi-parameter operator: 1 yes, 0 JH_ERR_UNSUPPORTED as before, the caller runs the composite stage by stage; same bits), "dense_combine" (round 6: operators whose non-zero blocks are
+ * "dense_list_rl_min" (log2 of the fewest row lanes per workgroup of that pass, 0: automatic), "red_blocks_wave" (round 6: jh_norm_blocks / jh_dot_blocks of many blocks of at most 16 KiB with a wave per block in one launch: 1 yes, 0 a workgroup per block + the fold; within the reductions' tolerance of each other), "adj_bare_chain" (round 6: jh_blockop_mul_adj and jh_blockop_normal_mul of a tall operator with rows of several kinds, or rows off the 16-byte grid, of up to 4 MiB on the chain kernels with empty stage lists -- packed row records --: 1 yes, 0 the MIXED tall kernel; same bits unless the split walk's part count changes), "adj_thin_mixed" (round 6: the adjoint of a tall operator with rows of several kinds on thin workgroups when fat ones would leave CUs idle -- rows of 1-8 MiB --: 1 yes, 0 round 5's shapes; same bits unless the split walk's part count changes), "grid_normal" (round 6: jh_blockop_normal_mul on N x (2 .. 4) grids of equal elementwise blocks -- diagonals, zero / identity / scalar blocks -- in one pass: 1 yes, 2 grids of plain diagonals only, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_step" (jh_blockop_bidiag_step, jh_lsqr_solve and jh_cgls_solve on N x (2 .. 4) grids of equal elementwise blocks in one pass per step: 1 yes, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_chain_step" (jh_chain_bidiag_step, jh_lsqr_solve_chain and jh_cgls_solve_chain on a FORWARD chain through an N x (2 .. 4) grid in one pass per step: 1 yes, 0 -- the default -- JH_ERR_UNSUPPORTED as before; same bits: see jh_chain_create, GRID CHAIN STEP), "grid_chain" (jh_chain_create on N x (2 .. 4) grids of equal elementwise blocks -- fused chains A' o W o A, (W o A)', W o A through a multi-parameter operator: 1 yes, 0 JH_ERR_UNSUPPORTED as before, the caller runs the composite stage by stage; same bits), "dense_combine" (round 6: operators whose non-zero blocks are
  * all DENSE children sum the products of a block line from CSR lists in one launch: 1 yes, 0 the general step lists; same bits);
  * round 4: "cg_dev" (jh_cgls_solve / jh_cgnr_solve with the recurrences on the device, graph-replayed unless lsqr_graph = 0: 1 automatic -- CGLS
  * like lsqr_graph, CG through the fused A'A up to 2 GiB of coefficients --, 2 at any size, 0 never: the host loops; within solver tolerance
@@ -656,7 +665,7 @@ int jh_team_normal_mul(int n, const jh_blockop *const *ops, jh_bvec *const *ys, 
  * "small_loop_max_kib" (operators of SMALL dense children whose matrices together reach this many KiB take
  * the list route instead of the one-launch loop: 512);
  * jh_tune_get also reads the counters "last_fwd_walk" (grid walk of the latest tall forward: 0 sequential, 1 all rows, 2 column bands),
- * "last_fwd_rows_per_wg", "last_adj_launches", "last_adj_parts", "last_grid_chain_shape" (how the latest grid chain was launched: see jh_chain_create), "last_grid_step_shape" (how the latest grid step was launched: see jh_blockop_bidiag_step), "last_step_chain" (row chunks of the latest one-pass step, 0: the plain walk), "graph_replays", "last_lsqr_graph" / "last_cg_graph" (graph replays of the latest
+ * "last_fwd_rows_per_wg", "last_adj_launches", "last_adj_parts", "last_grid_chain_shape" (how the latest grid chain was launched: see jh_chain_create), "last_grid_step_shape" (how the latest grid step was launched: see jh_blockop_bidiag_step), "last_grid_chain_step_shape" (how the latest grid chain step was launched: bit 0 nontemporal loads, bit 1 rows in parts; see jh_chain_create), "last_step_chain" (row chunks of the latest one-pass step, 0: the plain walk), "graph_replays", "last_lsqr_graph" / "last_cg_graph" (graph replays of the latest
  * jh_lsqr_solve / jh_cgls_solve or jh_cgnr_solve; 0: the host loop ran) and "last_dense_fused" (1: the latest dense adjoint / wide forward took the
  * fused launch). */
 int jh_tune_set(const char *name, int64_t value);

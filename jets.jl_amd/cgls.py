@@ -40,7 +40,7 @@ def cgls_core(eng, b, x0, damp, atol, btol, maxiter, overwrite_b=False, force_ma
     r = b if overwrite_b else eng.copy(eng.zeros_rng(), b)
     bnorm = eng.norm_rng(b)
     rnorm = eng.fwd(r, x, -1.0, 1.0) if x0 is not None else bnorm          # r = b - A x0
-    # an engine with a one-pass step AND a `normal` hook that asks for it (`step_cgls`: a weighted shard or team, lsqr._ShardEngine / _TeamEngine)
+    # an engine with a one-pass step AND a `normal` hook that asks for it (`step_cgls`: a weighted shard or team, lsqr._ShardEngine / _TeamEngine; one GPU: a weighted grid with the knob grid_chain_step = 1)
     # runs the two passes of jh_lsqr.hip's cgls_impl: delta = <p, A'A p> through the hook, then r <- r - alpha A p, ||r|| and A'r in one step --
     # no q.  Should the step decline (before anything is touched), the textbook passes take over from that iteration on.
     two_pass = bool(getattr(eng, "step_cgls", False))

@@ -657,12 +657,20 @@ def try_sum(out, x, ops: Sequence[Jop], sgns: Sequence[str], transposed: bool, w
 
 
 # ------------------------------------------------------------------------------ the solvers on a chain ----
+def grid_step_enabled() -> bool:
+    """Does the library take the one-pass step of a FORWARD chain through a grid (knob grid_chain_step = 1; the default is 0)?"""
+    from .device import tune_get
+
+    return tune_get("grid_chain_step") == 1
+
+
 class SolverChains:
     """The fused routes of the one-GPU solvers (lsqr.py, cgls.py) on a composite L = R o A o P that the planner turns into ONE FORWARD run
     (W o A, a block-diagonal @blockop of weights o A, W o A o M, a * (W o A)): `fwd` is its ChainHandle -- the Golub-Kahan step
     (jh_chain_bidiag_step) and the native solves (jh_*_solve_chain) take it --, `normal()` the NORMAL chain of adjoint(L) o L (cgnr_core's hook).
-    Through an N x K grid (fwd.grid) there is no one-pass step: step() declines without calling the library, LSQR / CGLS keep their two
-    passes (two fused grid chains), CGNR takes jh_cgnr_solve_chain or the NORMAL hook.
+    Through an N x K grid (fwd.grid) the one-pass step is behind the knob grid_chain_step (jh_grid_chain_step.hip; default 0): with 1, step() and
+    the native LSQR / CGLS solves take it like a tall chain's; with 0, step() declines without calling the library, LSQR / CGLS keep their
+    two passes (two fused grid chains).  CGNR takes jh_cgnr_solve_chain or the NORMAL hook either way.
     fwd is None when L is not one such run, the library declines, or JETS_CHAIN_STEP=0 (today's route: the chain into a range temporary, then
     the ADJOINT chain)."""
 
@@ -683,7 +691,7 @@ class SolverChains:
     def step(self, u, v, w, alpha: float, beta: float):
         """u <- alpha L v + beta u ; w <- L'u ; returns ||u||^2, or None when the library declines (R and R^H above four stages: the caller
         keeps the two halves)."""
-        if self.fwd.grid:
+        if self.fwd.grid and not grid_step_enabled():
             return None
         out = C.c_double(0)
         try:
@@ -694,6 +702,8 @@ class SolverChains:
             self.fwd = None
             return None
         STATS["chain_step_calls"] += 1
+        if self.fwd.grid:
+            STATS["grid_chain_calls"] += 1
         return out.value
 
     def normal_planned(self) -> bool:

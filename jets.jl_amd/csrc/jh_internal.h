@@ -145,6 +145,8 @@ struct jh_context {
     int64_t last_grid_chain_shape = 0; // how the most recent grid chain was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts, bit 2 the stages after A' on the folded parts
     int64_t grid_step = 1;             // knob: jh_blockop_bidiag_step (and the LSQR / CGLS loops of jh_lsqr_solve / jh_cgls_solve) on an N x (2 .. 4) grid of equal elementwise blocks in one pass (jh_grid_step.hip): 1 yes, 0 JH_ERR_UNSUPPORTED as before
     int64_t last_grid_step_shape = 0;  // how the most recent grid step was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
+    int64_t grid_chain_step = 0;       // knob: jh_chain_bidiag_step (and the LSQR / CGLS loops of jh_lsqr_solve_chain / jh_cgls_solve_chain) on a FORWARD chain through an N x (2 .. 4) grid in one pass (jh_grid_chain_step.hip): 1 yes, 0 (default) JH_ERR_UNSUPPORTED as before
+    int64_t last_grid_chain_step_shape = 0;   // how the most recent grid chain step was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
     int64_t fwd_anchor = -1;           // knob: the tall forward of rows that are not whole packs on lanes anchored to each row's own 16-byte grid (k_tall_fwd_anchored): -1 from 64 KiB rows on, 0 never, 1 always
     int64_t wide_twin = 1;             // knob: wide elementwise operators on their tall twin: 0 never (general kernels), 1 adjoint always + forward from 16 MiB blocks, 2 both always (tests)
     const double *step_coef_dev = nullptr;   // internal, set around the calls of the graph-captured LSQR loop: the one-pass step reads (alpha, beta) from
@@ -173,9 +175,12 @@ namespace jhb {   // jh_grid_step.hip: the one-pass Golub-Kahan step of an N x (
 bool grid_step_ok(const jh_blockop *op, const void *u, const void *v, const void *w);
 int grid_step(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq);
 }
+namespace jhb {   // jh_grid_chain_step.hip: the one-pass Golub-Kahan step of a FORWARD chain through an N x (2 .. 4) grid (knob grid_chain_step; the checks are jh_chain_bidiag_step's)
+int grid_chain_step(const jh_chain *ch, void *u, const void *v, void *w, double alpha, double beta, double *normsq);
+}
 namespace jhb {   // jh_tall_chain.hip: L' (JH_CHAIN_ADJOINT) / L'L (JH_CHAIN_NORMAL) of a FORWARD chain; the checks of the solvers on a chain (op: its operator)
 int chain_apply_derived(const jh_chain *fwd, int which, jh_bvec *out, const jh_bvec *in);
-int chain_solver_ok(const jh_chain *fwd, const jh_bvec *u, const jh_bvec *x, const jh_blockop **op, bool needs_step = true);   // needs_step: the loop takes jh_chain_bidiag_step (LSQR, CGLS; a grid chain has none)
+int chain_solver_ok(const jh_chain *fwd, const jh_bvec *u, const jh_bvec *x, const jh_blockop **op, bool needs_step = true);   // needs_step: the loop takes jh_chain_bidiag_step (LSQR, CGLS; a grid chain has it with the knob grid_chain_step = 1)
 }
 inline bool jh_stream_nt(double working_set_bytes)
 {

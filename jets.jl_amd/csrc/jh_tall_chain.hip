@@ -301,23 +301,27 @@ static int fwd_ready(const jh_chain *ch, const char *fn)
     return JH_OK;
 }
 
-// u <- alpha L v + beta u ;  w = L'u ;  ||u||^2 for L = R o A o P, in ONE pass (k_chain_adj MODE 2)
+// u <- alpha L v + beta u ;  w = L'u ;  ||u||^2 for L = R o A o P, in ONE pass (k_chain_adj MODE 2; through a grid, knob grid_chain_step = 1:
+// k_grid_chain_step, jh_grid_chain_step.hip)
 int jh_chain_bidiag_step(const jh_chain *fwd, jh_bvec *u, const jh_bvec *v, jh_bvec *w, double alpha, double beta, double *normsq)
 {
     JH_REQUIRE(fwd && u && v && w, "jh_chain_bidiag_step: null argument");
     JH_REQUIRE(fwd->type == JH_CHAIN_FORWARD, "jh_chain_bidiag_step: needs a FORWARD chain (got type %d)", fwd->type);
-    if (fwd->ncol > 1) return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step: a grid chain has no one-pass step (run the FORWARD chain, then the ADJOINT)");
-    if (!fwd->nrm_ok)
-        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step: R and R^H need more than %d range-side stages", JH_CHAIN_MAX_STAGES);
     const jh_blockop *op = fwd->op;
     JH_TRY(jh_enter(op, u, v, w));
+    const bool grid = fwd->ncol > 1;
+    if (grid && jh_ctx().grid_chain_step == 0)
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step: a grid chain's one-pass step is off (knob grid_chain_step; run the FORWARD chain, then the ADJOINT)");
+    if (!fwd->nrm_ok)
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step: R and R^H need more than %d range-side stages", JH_CHAIN_MAX_STAGES);
     const int64_t nrange = op->row_off[(size_t)op->nrow], ndom = op->col_off[(size_t)op->ncol];
     JH_REQUIRE(u->dtype == op->dtype && v->dtype == op->dtype && w->dtype == op->dtype, "jh_chain_bidiag_step: dtype mismatch");
     JH_REQUIRE(u->length == nrange && v->length == ndom && w->length == ndom, "jh_chain_bidiag_step: u must be a range vector, v and w domain vectors of the operator");
     JH_REQUIRE(w->data != v->data && u->data != v->data && u->data != w->data, "jh_chain_bidiag_step: u, v and w must be three vectors");
-    if (!jhb::tall_unaligned_ok(op, u->data, v->data) || !jhb::tall_unaligned_ok(op, nullptr, w->data))
+    if (!chain_vectors_ok(fwd, u->data, v->data) || !chain_vectors_ok(fwd, nullptr, w->data))
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step: a vector or coefficient array is not aligned like its scalar");
     JH_TRY(fwd_ready(fwd, "jh_chain_bidiag_step"));
+    if (grid) return jhb::grid_chain_step(fwd, u->data, v->data, w->data, alpha, beta, normsq);
     return jhb::chain_launch_step(fwd, fwd->step_args, u->data, v->data, w->data, alpha, beta, normsq, 0, w->length, false);
 }
 
@@ -383,8 +387,9 @@ namespace jhb {
 int chain_solver_ok(const jh_chain *fwd, const jh_bvec *u, const jh_bvec *x, const jh_blockop **op, bool needs_step)
 {
     JH_REQUIRE(fwd->type == JH_CHAIN_FORWARD, "jh_*_solve_chain: needs a FORWARD chain (got type %d)", fwd->type);
-    if (needs_step && fwd->ncol > 1)
-        return jh_fail(JH_ERR_UNSUPPORTED, "jh_*_solve_chain: a grid chain has no one-pass step (LSQR / CGLS keep their two-pass loops; CGNR runs)");
+    const jh_context *cx = jh_ctx_by_id(fwd->ctx);                              // (the handle's context: the caller enters it after these checks)
+    if (needs_step && fwd->ncol > 1 && !(cx && cx->grid_chain_step == 1))
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_*_solve_chain: a grid chain's one-pass step is off (knob grid_chain_step: LSQR / CGLS keep their two-pass loops; CGNR runs)");
     if (!fwd->nrm_ok)
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_*_solve_chain: R and R^H need more than %d range-side stages", JH_CHAIN_MAX_STAGES);
     const jh_blockop *o = fwd->op;

@@ -176,12 +176,21 @@ class _Engine:
         r = self._step_local(u, v, alpha, beta)
         return None if r is None else (math.sqrt(r[0]), r[1])
 
+    @property
+    def step_cgls(self) -> bool:
+        """cgls_core takes its two-pass form -- <p, L'L p> through the NORMAL chain's hook, then r <- r - alpha L p, ||r|| and L'r in one step, the
+        passes of jh_cgls_solve_chain -- on a FORWARD chain through a grid whose one-pass step is on (knob grid_chain_step = 1)."""
+        return (self.chains is not None and self.chains.fwd is not None and self.chains.fwd.grid and self.fused_step
+                and getattr(self, "normal", None) is not None and _chn.grid_step_enabled())
+
     def native_solver(self, solver: str):
         """The whole `solver` loop behind the C ABI ("lsqr", "cgls" or "cgnr"): (entry point, its leading arguments, the chains.STATS counters a
         finished solve bumps), or None (lsqr_core / cgls_core / cgnr_core then run).  One FORWARD chain: jh_*_solve_chain on its handle; a bare
         grid or the tall operator: jh_*_solve."""
         if self.chains is not None and self.chains.fwd is not None:
             fwd = self.chains.fwd
+            if fwd.grid and solver != "cgnr" and not _chn.grid_step_enabled():
+                return None                               # (LSQR / CGLS through a grid iterate on its one-pass step: knob grid_chain_step)
             return getattr(lib, f"jh_{solver}_solve_chain"), (fwd.handle,), ("chain_solve_calls",) + (("grid_chain_calls",) if fwd.grid else ())
         if self.grid is not None:
             return getattr(lib, f"jh_{solver}_solve"), (self.grid.handle,), ("grid_solve_calls",) if solver != "cgnr" else ()

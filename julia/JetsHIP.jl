@@ -1031,7 +1031,7 @@ end
 function bidiag_step!(u::BlockArray{T,<:HipArray{T}}, w::HipArray{T}, A::JopLn, v::HipArray{T}, alpha::Real, beta::Real) where {T}
     h = tall_native(A, T)
     h == C_NULL && (h = grid_native(A, T))
-    h == C_NULL && return bidiag_step!(u, w, _plan_chain(A, T; grid=false), v, alpha, beta)   # (a grid chain has no one-pass step)
+    h == C_NULL && return bidiag_step!(u, w, _plan_chain(A, T; grid=(tune_get("grid_chain_step") == 1)), v, alpha, beta)   # (a grid chain's one-pass step: knob grid_chain_step)
     nrm2 = Ref{Cdouble}()
     check(ccall((:jh_blockop_bidiag_step, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ref{Cdouble}),
                 h, handle(u), handle(v), handle(w), alpha, beta, nrm2))
@@ -1041,7 +1041,7 @@ end
 # 1138-1154): u <- alpha*(L v) + beta*u ; w <- L'u ; ||u|| in ONE pass over A, the weights and u (jh_chain_bidiag_step)
 function bidiag_step!(u::BlockArray{T,<:HipArray{T}}, w::HipArray{T}, chain::Ptr{Cvoid}, v::HipArray{T}, alpha::Real, beta::Real) where {T}
     chain == C_NULL && error("bidiag_step!: needs a tall block operator, an N x (2 .. 4) block operator, or a composite that is one fused FORWARD chain through a tall operator " *
-                             "(a weighted N x K grid has no one-pass step)")
+                             "(through an N x K grid: knob grid_chain_step = 1)")
     nrm2 = Ref{Cdouble}()
     check(ccall((:jh_chain_bidiag_step, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ref{Cdouble}),
                 chain, handle(u), handle(v), handle(w), alpha, beta, nrm2))
@@ -1067,7 +1067,8 @@ end
 
 # the FORWARD chain handle of a composite that plans to ONE fused run R ∘ A ∘ P (W ∘ A, W ∘ A ∘ M, a * (W ∘ A)), or C_NULL: what the solvers below take
 # in place of a tall block operator (jh_*_solve_chain)
-# grid = false: not a chain through an N x K grid (those have no one-pass Golub-Kahan step: jh_lsqr_solve_chain / jh_cgls_solve_chain decline them)
+# grid = false: not a chain through an N x K grid (their one-pass Golub-Kahan step is behind the knob grid_chain_step, default 0: without it
+# jh_chain_bidiag_step, jh_lsqr_solve_chain and jh_cgls_solve_chain decline them; the ranged step declines them always)
 function _plan_chain(L::Jop, ::Type{T}; grid::Bool=true) where {T}
     (L isa JopLn && jet(L).df! === JetComposite_df!) || return C_NULL
     ops = state(L).ops
@@ -1087,9 +1088,9 @@ struct jh_lsqr_result; istop::Int32; itn::Int32; r1norm::Cdouble; r2norm::Cdoubl
 function hip_lsqr!(x::HipArray{T}, A::JopLn, b::BlockArray{T,<:HipArray{T}}; x0::Bool=false, damp=0.0, atol=1e-6, btol=1e-6, conlim=1e8, maxiter=100, partitioned::Bool=false) where {T}
     h = tall_native(A, T)
     (h == C_NULL && !partitioned) && (h = grid_native(A, T))                  # a bare N x (2 .. 4) grid: the loop on its one-pass step (one GPU; the library declines the kinds it has no kernel for)
-    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T; grid=false) : C_NULL   # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain
+    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T; grid=(tune_get("grid_chain_step") == 1)) : C_NULL   # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain (through a grid: knob grid_chain_step)
     h == C_NULL && c == C_NULL && error("hip_lsqr!: needs a tall block operator of device-native children, an N x (2 .. 4) block operator (one GPU), or a composite that is one fused FORWARD chain " *
-                                        "through a tall operator (a weighted N x K grid has no one-pass step: use hip_cgnr!, or IterativeSolvers on the composite, whose mul! runs the fused grid chains)")
+                                        "through a tall operator (a weighted N x K grid takes its one-pass step with the knob grid_chain_step = 1; otherwise use hip_cgnr!, or IterativeSolvers on the composite, whose mul! runs the fused grid chains)")
     res = Ref{jh_lsqr_result}()
     hist = Vector{Cdouble}(undef, 2 * maxiter)
     if c != C_NULL
@@ -1112,9 +1113,9 @@ end
 function hip_cgls!(x::HipArray{T}, A::JopLn, b::BlockArray{T,<:HipArray{T}}; x0::Bool=false, damp=0.0, atol=1e-6, btol=1e-6, maxiter=100, partitioned::Bool=false) where {T}
     h = tall_native(A, T)
     (h == C_NULL && !partitioned) && (h = grid_native(A, T))                  # a bare N x (2 .. 4) grid: the loop on its one-pass step (one GPU; the library declines the kinds it has no kernel for)
-    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T; grid=false) : C_NULL   # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain
+    c = (h == C_NULL && !partitioned) ? _plan_chain(A, T; grid=(tune_get("grid_chain_step") == 1)) : C_NULL   # a weighted composite W ∘ A ∘ M: the loop on its FORWARD chain (through a grid: knob grid_chain_step)
     h == C_NULL && c == C_NULL && error("hip_cgls!: needs a tall block operator of device-native children, an N x (2 .. 4) block operator (one GPU), or a composite that is one fused FORWARD chain " *
-                                        "through a tall operator (a weighted N x K grid has no one-pass step: use hip_cgnr!, or IterativeSolvers on the composite, whose mul! runs the fused grid chains)")
+                                        "through a tall operator (a weighted N x K grid takes its one-pass step with the knob grid_chain_step = 1; otherwise use hip_cgnr!, or IterativeSolvers on the composite, whose mul! runs the fused grid chains)")
     res = Ref{jh_lsqr_result}()
     hist = Vector{Cdouble}(undef, 2 * max(maxiter, 1))
     if c != C_NULL
