@@ -305,7 +305,22 @@ int jh_blockop_f(const jh_blockop *op, jh_bvec *d, const jh_bvec *m);
 int jh_blockop_point(jh_blockop *op, const jh_bvec *mo);
 /* The same adjoint restricted to the elements [first_elem, first_elem+count) of the domain vector (16-byte aligned
  * bounds -- the last range may end with the vector instead --; tall operators of elementwise rows): lets a multi-GPU host pipeline the exchange chunk by chunk -- all-reduce chunk k
- * while the kernel computes chunk k+1.  Results are identical to jh_blockop_mul_adj on those elements. */
+ * while the kernel computes chunk k+1.  Results are identical to jh_blockop_mul_adj on those elements.
+ * GRID RANGE (knob "grid_range" = 1; the default is 0, with which a grid returns JH_ERR_UNSUPPORTED as before): this call, jh_blockop_normal_mul_range and
+ * jh_blockop_bidiag_step_range also take the N x K grids of jh_blockop_bidiag_step (N >= 2, K = 2 .. 4, equal elementwise blocks of >= 16 bytes, no
+ * nonlinear child).  On a grid [first_elem, first_elem + count) are positions INSIDE a block, 0 <= first_elem, first_elem + count <= n (the block
+ * length) -- not positions of the flat K n domain slab: a row's forward sum needs all K of v_k[p], so flat ranges do not decompose.  One call reads
+ * those positions of every range block and writes the K pieces [k n + first_elem, k n + first_elem + count), k = 0 .. K - 1, of the domain-side output and
+ * nothing else (a host that exchanges a finished range sends those K pieces).  first_elem * s must be a multiple of 16 bytes, count * s too unless the
+ * range ends with the block (blocks off the 16-byte grid are taken: the partial last pack belongs to the range that ends the block); count == 0 does
+ * nothing; anything else is JH_ERR_INVALID before anything is touched.  Values: u has the bits of the whole-vector call always; the domain-side output
+ * has them where both walk the rows in one part (always with knob adj_split = 0) -- a range is launched as a vector of its own length, so many rows
+ * of small blocks may be cut into other parts than the whole vector's (tolerance parity).  The nontemporal rule is the whole-vector call's, over the
+ * whole call's bytes.  The whole-vector calls' own knobs hold for their ranged forms too: jh_blockop_normal_mul_range declines a grid that "grid_normal"
+ * keeps from jh_blockop_normal_mul (0: every grid; 2: grids of several kinds), jh_blockop_bidiag_step_range one that "grid_step" = 0 keeps from
+ * jh_blockop_bidiag_step; the ranged adjoint depends on "grid_range" alone.  Counter "last_grid_range_shape": bit 0 nontemporal loads, bit 1 rows in parts.  jh_*_solve_partitioned / _team, jh_team_mul_adj /
+ * jh_team_normal_mul and the graph-replayed loops decline grids under either setting, and jh_chain_apply_range / jh_chain_bidiag_step_range on a grid
+ * chain stay refused. */
 int jh_blockop_mul_adj_range(const jh_blockop *op, jh_bvec *m, const jh_bvec *d, int64_t first_elem, int64_t count);
 /* (A' o A) m -> JetComposite_df! over (A', A), src/Jets.jl:530-534, fused: A's coefficients are read
  * once and the range-side intermediate is never materialised.  Same rounding sequence as the
@@ -316,7 +331,8 @@ int jh_blockop_mul_adj_range(const jh_blockop *op, jh_bvec *m, const jh_bvec *d,
 int jh_blockop_normal_mul(const jh_blockop *op, jh_bvec *y, const jh_bvec *m);
 /* The same fused A'A restricted to the elements [first_elem, first_elem+count) of the domain (16-byte aligned bounds): for a host
  * that pipelines the exchange of y range by range against the kernels -- CG on the normal equations over a row partition
- * (jh_cgnr_solve_partitioned / _team do exactly that).  Identical to jh_blockop_normal_mul on those elements. */
+ * (jh_cgnr_solve_partitioned / _team do exactly that).  Identical to jh_blockop_normal_mul on those elements.  An N x (2 .. 4) grid with the knob
+ * "grid_range" = 1: the range is positions inside a block and the K pieces y_k[first_elem, first_elem + count) are written (GRID RANGE, jh_blockop_mul_adj_range). */
 int jh_blockop_normal_mul_range(const jh_blockop *op, jh_bvec *y, const jh_bvec *m, int64_t first_elem, int64_t count);
 /* JetSum of tall operators, src/Jets.jl:628-655, fused: d = sum_k sign_k*(scale_k*(A_k m)) and its adjoint
  * m = sum_k sign_k*(A_k'(scale_k d)) for tall all-DIAG operators of identical shape, ANY number of them (four per launch, later
@@ -485,7 +501,9 @@ int jh_blockop_bidiag_step(const jh_blockop *op, jh_bvec *u, const jh_bvec *v, j
 /* The same step restricted to the elements [first_elem, first_elem+count) of the domain (16-byte aligned bounds): updates
  * those columns of every row of u, writes that range of w, and returns that range's share of ||u||^2 (the shares add up).
  * Lets a row-partitioned multi-GPU solver all-reduce chunk k of w while chunk k+1 is being computed.  Identical values
- * to jh_blockop_bidiag_step on those elements.  Tall operators only: a grid returns JH_ERR_UNSUPPORTED. */
+ * to jh_blockop_bidiag_step on those elements.  Tall operators only: a grid returns JH_ERR_UNSUPPORTED -- unless the knob "grid_range" is 1
+ * (GRID RANGE, jh_blockop_mul_adj_range): then the range is positions inside a block, those positions of every u_i are updated, the K pieces
+ * w_k[first_elem, first_elem + count) are written and the range's share of ||u||^2 is returned or (normsq == NULL) deferred as below. */
 int jh_blockop_bidiag_step_range(const jh_blockop *op, jh_bvec *u, const jh_bvec *v, jh_bvec *w, double alpha, double beta,
                                  int64_t first_elem, int64_t count, double *normsq);
 /* Deferred ||u||^2 for a step enqueued range by range: with normsq == NULL jh_blockop_bidiag_step_range does not synchronise;
@@ -642,7 +660,7 @@ int jh_team_normal_mul(int n, const jh_blockop *const *ops, jh_bvec *const *ys, 
  * aligned loads of diagonals laid out like the range vector: -1 rows of 64 KiB or more, 0 never, 1 always; same bits), "tall_f" (F(m) of a tall nonlinear operator of elementwise children -- jh_blockop_f -- on the tall tiling: 1 yes, 0 the
  * general kernels; same bits), "dense_list_shared" (round 6: the rows pass of y = B x for DENSE children whose columns are off the 16-byte grid numbers its
  * chunks XCD by XCD and loads temporally, so the 128-byte line two neighbouring rows share is fetched from HBM once: 1 yes, 0 round 5's pass; same bits),
- * "dense_list_rl_min" (log2 of the fewest row lanes per workgroup of that pass, 0: automatic), "red_blocks_wave" (round 6: jh_norm_blocks / jh_dot_blocks of many blocks of at most 16 KiB with a wave per block in one launch: 1 yes, 0 a workgroup per block + the fold; within the reductions' tolerance of each other), "adj_bare_chain" (round 6: jh_blockop_mul_adj and jh_blockop_normal_mul of a tall operator with rows of several kinds, or rows off the 16-byte grid, of up to 4 MiB on the chain kernels with empty stage lists -- packed row records --: 1 yes, 0 the MIXED tall kernel; same bits unless the split walk's part count changes), "adj_thin_mixed" (round 6: the adjoint of a tall operator with rows of several kinds on thin workgroups when fat ones would leave CUs idle -- rows of 1-8 MiB --: 1 yes, 0 round 5's shapes; same bits unless the split walk's part count changes), "grid_normal" (round 6: jh_blockop_normal_mul on N x (2 .. 4) grids of equal elementwise blocks -- diagonals, zero / identity / scalar blocks -- in one pass: 1 yes, 2 grids of plain diagonals only, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_step" (jh_blockop_bidiag_step, jh_lsqr_solve and jh_cgls_solve on N x (2 .. 4) grids of equal elementwise blocks in one pass per step: 1 yes, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_chain_step" (jh_chain_bidiag_step, jh_lsqr_solve_chain and jh_cgls_solve_chain on a FORWARD chain through an N x (2 .. 4) grid in one pass per step: 1 yes, 0 -- the default -- JH_ERR_UNSUPPORTED as before; same bits: see jh_chain_create, GRID CHAIN STEP), "grid_chain" (jh_chain_create on N x (2 .. 4) grids of equal elementwise blocks -- fused chains A' o W o A, (W o A)', W o A through a multi-parameter operator: 1 yes, 0 JH_ERR_UNSUPPORTED as before, the caller runs the composite stage by stage; same bits), "dense_combine" (round 6: operators whose non-zero blocks are
+ * "dense_list_rl_min" (log2 of the fewest row lanes per workgroup of that pass, 0: automatic), "red_blocks_wave" (round 6: jh_norm_blocks / jh_dot_blocks of many blocks of at most 16 KiB with a wave per block in one launch: 1 yes, 0 a workgroup per block + the fold; within the reductions' tolerance of each other), "adj_bare_chain" (round 6: jh_blockop_mul_adj and jh_blockop_normal_mul of a tall operator with rows of several kinds, or rows off the 16-byte grid, of up to 4 MiB on the chain kernels with empty stage lists -- packed row records --: 1 yes, 0 the MIXED tall kernel; same bits unless the split walk's part count changes), "adj_thin_mixed" (round 6: the adjoint of a tall operator with rows of several kinds on thin workgroups when fat ones would leave CUs idle -- rows of 1-8 MiB --: 1 yes, 0 round 5's shapes; same bits unless the split walk's part count changes), "grid_normal" (round 6: jh_blockop_normal_mul on N x (2 .. 4) grids of equal elementwise blocks -- diagonals, zero / identity / scalar blocks -- in one pass: 1 yes, 2 grids of plain diagonals only, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_step" (jh_blockop_bidiag_step, jh_lsqr_solve and jh_cgls_solve on N x (2 .. 4) grids of equal elementwise blocks in one pass per step: 1 yes, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_chain_step" (jh_chain_bidiag_step, jh_lsqr_solve_chain and jh_cgls_solve_chain on a FORWARD chain through an N x (2 .. 4) grid in one pass per step: 1 yes, 0 -- the default -- JH_ERR_UNSUPPORTED as before; same bits: see jh_chain_create, GRID CHAIN STEP), "grid_range" (jh_blockop_mul_adj_range, jh_blockop_normal_mul_range and jh_blockop_bidiag_step_range on N x (2 .. 4) grids of equal elementwise blocks, the range being positions inside a block: 1 yes, 0 -- the default -- JH_ERR_UNSUPPORTED as before; see jh_blockop_mul_adj_range, GRID RANGE), "grid_chain" (jh_chain_create on N x (2 .. 4) grids of equal elementwise blocks -- fused chains A' o W o A, (W o A)', W o A through a multi-parameter operator: 1 yes, 0 JH_ERR_UNSUPPORTED as before, the caller runs the composite stage by stage; same bits), "dense_combine" (round 6: operators whose non-zero blocks are
  * all DENSE children sum the products of a block line from CSR lists in one launch: 1 yes, 0 the general step lists; same bits);
  * round 4: "cg_dev" (jh_cgls_solve / jh_cgnr_solve with the recurrences on the device, graph-replayed unless lsqr_graph = 0: 1 automatic -- CGLS
  * like lsqr_graph, CG through the fused A'A up to 2 GiB of coefficients --, 2 at any size, 0 never: the host loops; within solver tolerance
@@ -665,7 +683,7 @@ int jh_team_normal_mul(int n, const jh_blockop *const *ops, jh_bvec *const *ys, 
  * "small_loop_max_kib" (operators of SMALL dense children whose matrices together reach this many KiB take
  * the list route instead of the one-launch loop: 512);
  * jh_tune_get also reads the counters "last_fwd_walk" (grid walk of the latest tall forward: 0 sequential, 1 all rows, 2 column bands),
- * "last_fwd_rows_per_wg", "last_adj_launches", "last_adj_parts", "last_grid_chain_shape" (how the latest grid chain was launched: see jh_chain_create), "last_grid_step_shape" (how the latest grid step was launched: see jh_blockop_bidiag_step), "last_grid_chain_step_shape" (how the latest grid chain step was launched: bit 0 nontemporal loads, bit 1 rows in parts; see jh_chain_create), "last_step_chain" (row chunks of the latest one-pass step, 0: the plain walk), "graph_replays", "last_lsqr_graph" / "last_cg_graph" (graph replays of the latest
+ * "last_fwd_rows_per_wg", "last_adj_launches", "last_adj_parts", "last_grid_chain_shape" (how the latest grid chain was launched: see jh_chain_create), "last_grid_step_shape" (how the latest grid step was launched: see jh_blockop_bidiag_step), "last_grid_chain_step_shape" (how the latest grid chain step was launched: bit 0 nontemporal loads, bit 1 rows in parts; see jh_chain_create), "last_grid_range_shape" (how the latest ranged grid call was launched: bit 0 nontemporal loads, bit 1 rows in parts; see jh_blockop_mul_adj_range), "last_step_chain" (row chunks of the latest one-pass step, 0: the plain walk), "graph_replays", "last_lsqr_graph" / "last_cg_graph" (graph replays of the latest
  * jh_lsqr_solve / jh_cgls_solve or jh_cgnr_solve; 0: the host loop ran) and "last_dense_fused" (1: the latest dense adjoint / wide forward took the
  * fused launch). */
 int jh_tune_set(const char *name, int64_t value);

@@ -58,7 +58,11 @@ def cgls_core(eng, b, x0, damp, atol, btol, maxiter, overwrite_b=False, force_ma
         while itn < maxiter:
             itn += 1
             if two_pass:
-                delta = eng.normal(y, p) + (damp * eng.norm_dom(p)) ** 2    # <p, A'A p> in one pass
+                pap = getattr(eng, "normal_cgls", eng.normal)(y, p)         # <p, A'A p> in one pass (normal_cgls: a hook that exchanges the scalar only -- y is not used further)
+                if pap is None:                                             # (the hook's kernel was declined before anything was touched: the textbook passes)
+                    two_pass, q = False, eng.zeros_rng()
+                    pap = eng.fwd(q, p, 1.0, 0.0) ** 2
+                delta = pap + (damp * eng.norm_dom(p)) ** 2
             else:
                 qn = eng.fwd(q, p, 1.0, 0.0)                                 # q = A p, ||q||
                 delta = qn * qn + (damp * eng.norm_dom(p)) ** 2

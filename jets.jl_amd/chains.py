@@ -36,7 +36,8 @@ STATS = {"chain_calls": 0, "sum_terms_fused": 0, "bcast_calls": 0,    # how ofte
          "chain_step_calls": 0, "chain_solve_calls": 0,               # the solvers on a FORWARD chain: one-pass steps (jh_chain_bidiag_step), whole native solves (jh_*_solve_chain)
          "chain_step_range_calls": 0,                                 # one-pass steps on an element range (jh_chain_bidiag_step_range: weighted shards and teams; also in chain_range_calls)
          "grid_chain_calls": 0,                                       # fused runs through an N x (2 .. 4) grid (also counted in chain_calls / chain_solve_calls)
-         "grid_step_calls": 0, "grid_solve_calls": 0}                 # the solvers on a bare grid: one-pass steps (jh_blockop_bidiag_step), native LSQR / CGLS solves
+         "grid_step_calls": 0, "grid_solve_calls": 0,                 # the solvers on a bare grid: one-pass steps (jh_blockop_bidiag_step), native LSQR / CGLS solves
+         "grid_range_calls": 0}                                       # ranged calls on a bare grid (jh_blockop_{mul_adj,normal_mul,bidiag_step}_range with the knob grid_range = 1: sharded grids and teams)
 
 
 # ------------------------------------------------------------------------------ classification -----

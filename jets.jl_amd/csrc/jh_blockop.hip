@@ -656,6 +656,11 @@ int jh_blockop_mul_adj_range(const jh_blockop *op, jh_bvec *m, const jh_bvec *d,
     const bool mixed = !fast && (tall_mixed_ok(op, d->data, m->data) || tall_unaligned_ok(op, d->data, m->data));
     if (mixed && op->nonlinear && !op->pointed)
         return jh_fail(JH_ERR_STATE, "jh_blockop_mul_adj_range: operator has nonlinear blocks and no linearisation point (jh_blockop_point)");
+    // an N x (2 .. 4) grid of equal elementwise blocks (knob grid_range = 1): the range is positions INSIDE a block, the K pieces of it are written
+    if (!mixed && !fast && jhb::grid_range_ok(op, m->data, d->data, nullptr)) {
+        JH_TRY(jhb::grid_range_bounds(op, first_elem, count, "jh_blockop_mul_adj_range"));
+        return count == 0 ? JH_OK : jhb::grid_adj_range(op, m->data, d->data, first_elem, count);
+    }
     if (!mixed && !fast)
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_blockop_mul_adj_range: needs a tall operator of >= 2 equal elementwise rows");
     const int64_t es = (int64_t)jh_dtype_size(op->dtype);
@@ -703,6 +708,12 @@ int jh_blockop_normal_mul_range(const jh_blockop *op, jh_bvec *y, const jh_bvec 
     JH_REQUIRE(first_elem >= 0 && count >= 0 && first_elem + count <= y->length,
                "jh_blockop_normal_mul_range: elements [%lld, %lld) outside the domain vector (%lld elements)", (long long)first_elem,
                (long long)(first_elem + count), (long long)y->length);
+    // an N x (2 .. 4) grid of equal elementwise blocks (knob grid_range = 1): the range is positions INSIDE a block, the K pieces of it are written
+    // (and the whole-vector call's own knob: with grid_normal = 0, or 2 on a grid of several kinds, the ranged call declines what jh_blockop_normal_mul declines)
+    if (jhb::grid_range_ok(op, y->data, m->data, nullptr) && jhb::grid_normal_ok(op, y->data, m->data)) {
+        JH_TRY(jhb::grid_range_bounds(op, first_elem, count, "jh_blockop_normal_mul_range"));
+        return count == 0 ? JH_OK : jhb::grid_normal_range(op, y->data, m->data, first_elem, count);
+    }
     const int64_t es = (int64_t)jh_dtype_size(op->dtype);
     JH_REQUIRE((first_elem * es) % 16 == 0 && ((count * es) % 16 == 0 || first_elem + count == y->length),
                "jh_blockop_normal_mul_range: chunk boundaries must be 16-byte aligned (the last chunk may end with the vector)");

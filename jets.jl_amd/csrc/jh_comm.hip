@@ -508,6 +508,10 @@ static int team_ranged(const char *who, int n, const jh_blockop *const *ops, jh_
                    who, k, k, n);
         JH_REQUIRE(outs[k]->length == outs[0]->length && outs[k]->dtype == outs[0]->dtype, "%s: member %d's domain vector differs in length or element type", who, k);
     }
+    // (the ranges below are cut over the flat domain vector: a tall operator's.  A grid's ranged calls -- knob grid_range -- take positions inside a block,
+    // which the host's member loop cuts; here a grid is declined before anything is enqueued, under either setting of the knob, as before)
+    for (int k = 0; k < n; k++)
+        if (ops[k]->ncol != 1) return jh_fail(JH_ERR_UNSUPPORTED, "%s: needs tall operators of >= 2 equal elementwise rows", who);
     const int64_t len = outs[0]->length;
     int64_t step = (len + nranges - 1) / nranges;
     step = (step + 16383) / 16384 * 16384;                                 // range bounds on 64 KiB boundaries (as the solvers' exchange)

@@ -23,12 +23,13 @@ namespace {
 // the same walk over the PACKED table (MIXED grids): words[(i) * K + k]
 template <typename S, int E, int NS, int K, int DEPTH, bool NT>
 __global__ __launch_bounds__(256) void k_grid_normal_mixed(const jh_dev_block *__restrict__ blocks, const uint64_t *__restrict__ words, int64_t nrow, int64_t n_scalars,
-                                                           const S *__restrict__ m, S *__restrict__ y, int64_t rows_per_part, S *__restrict__ part_out)
+                                                           const S *__restrict__ m, S *__restrict__ y, int64_t rows_per_part, S *__restrict__ part_out,
+                                                           int64_t s_begin, int64_t s_end)
 {
     typedef typename vec_of<S, NS>::type V;
-    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;
-    const bool ok = s0 < n_scalars;
-    const int64_t sk = pack_start<NS>(ok ? s0 : 0, n_scalars);
+    const int64_t s0 = s_begin + ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;      // (the lanes cover [s_begin, s_end) of a block: k_grid_normal)
+    const bool ok = s0 < s_end;
+    const int64_t sk = pack_start<NS>(ok ? s0 : s_begin, s_end);
     V x[K], acc[K];
 #pragma unroll
     for (int k = 0; k < K; k++) {
@@ -113,12 +114,14 @@ __global__ __launch_bounds__(256) void k_grid_normal_mixed(const jh_dev_block *_
 
 template <typename S, int E, int NS, int K, int DEPTH, bool NT>
 __global__ __launch_bounds__(256) void k_grid_normal(const jh_dev_block *__restrict__ blocks, int64_t nrow, int64_t n_scalars, const S *__restrict__ m,
-                                                     S *__restrict__ y, int64_t rows_per_part, S *__restrict__ part_out)
+                                                     S *__restrict__ y, int64_t rows_per_part, S *__restrict__ part_out, int64_t s_begin, int64_t s_end)
 {
+    // the lanes cover the scalars [s_begin, s_end) of a block (the whole block: 0, n_scalars; a range of it: jh_blockop_normal_mul_range with the knob
+    // grid_range -- a range shorter than one pack ends with the block and is loaded from s_end - NS); n_scalars stays the stride of the pieces of m, y and the slabs
     typedef typename vec_of<S, NS>::type V;
-    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;
-    const bool ok = s0 < n_scalars;
-    const int64_t sk = pack_start<NS>(ok ? s0 : 0, n_scalars);
+    const int64_t s0 = s_begin + ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;
+    const bool ok = s0 < s_end;
+    const int64_t sk = pack_start<NS>(ok ? s0 : s_begin, s_end);
     V x[K], acc[K];
 #pragma unroll
     for (int k = 0; k < K; k++) {
@@ -177,14 +180,17 @@ __global__ __launch_bounds__(256) void k_grid_normal(const jh_dev_block *__restr
 }
 
 template <typename S, int E, int NS, int K, int DEPTH>
-int launch_grid_normal(const jh_blockop *op, void *y, const void *m)
+int launch_grid_normal(const jh_blockop *op, void *y, const void *m, int64_t first_elem, int64_t end_elem)
 {
     jh_context &c = jh_ctx();
-    const int64_t n_scalars = op->row_len[0] * E, packs = (n_scalars + NS - 1) / NS;
+    // end_elem < 0: the whole block; else the positions [first_elem, end_elem) of every block, launched as a vector of its own length
+    const bool ranged = end_elem >= 0;
+    const int64_t n_scalars = op->row_len[0] * E, s_begin = ranged ? first_elem * E : 0, s_end = ranged ? end_elem * E : n_scalars;
+    const int64_t packs = (s_end - s_begin + NS - 1) / NS;
     const int64_t gx = (packs + 255) / 256;
-    int64_t parts = jhb::pick_adj_parts(gx, op->nrow), rows_per_part = 0;
+    int64_t parts = s_end - s_begin < NS ? 1 : jhb::pick_adj_parts(gx, op->nrow), rows_per_part = 0;   // (a range shorter than one pack loads from before s_begin: one part)
     // (one workgroup per CU, up to two: the ordered walk is latency-bound there, as for the chains -- jh_tall_chain.hip)
-    if (parts == 1 && c.adj_split < 0 && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
+    if (parts == 1 && s_end - s_begin >= NS && c.adj_split < 0 && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
     void *slabs = nullptr;
     if (parts > 1) {
         rows_per_part = (op->nrow + parts - 1) / parts;
@@ -193,34 +199,39 @@ int launch_grid_normal(const jh_blockop *op, void *y, const void *m)
     }
     c.last_adj_parts = parts;
     c.last_adj_launches = 1;
-    const bool nt = jh_stream_nt((double)op->nrow * (double)K * (double)n_scalars * sizeof(S));
+    const bool nt = jh_stream_nt((double)op->nrow * (double)K * (double)n_scalars * sizeof(S));   // (a range too: the whole pass's bytes)
+    if (ranged) c.last_grid_range_shape = (nt ? 1 : 0) | (parts > 1 ? 2 : 0);
     if (!op->all_diag) {                                       // (the packed table for grids of plain diagonals too: within the noise of this kernel, profiles/bench_grid_normal_r06.txt)
         if (nt)
             hipLaunchKernelGGL((k_grid_normal_mixed<S, E, NS, K, DEPTH, true>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, op->dev_blocks,
-                               (const uint64_t *)op->grid_words, op->nrow, n_scalars, (const S *)m, (S *)y, rows_per_part, (S *)slabs);
+                               (const uint64_t *)op->grid_words, op->nrow, n_scalars, (const S *)m, (S *)y, rows_per_part, (S *)slabs, s_begin, s_end);
         else
             hipLaunchKernelGGL((k_grid_normal_mixed<S, E, NS, K, DEPTH, false>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, op->dev_blocks,
-                               (const uint64_t *)op->grid_words, op->nrow, n_scalars, (const S *)m, (S *)y, rows_per_part, (S *)slabs);
+                               (const uint64_t *)op->grid_words, op->nrow, n_scalars, (const S *)m, (S *)y, rows_per_part, (S *)slabs, s_begin, s_end);
     } else if (nt)
         hipLaunchKernelGGL((k_grid_normal<S, E, NS, K, DEPTH, true>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, op->dev_blocks, op->nrow,
-                           n_scalars, (const S *)m, (S *)y, rows_per_part, (S *)slabs);
+                           n_scalars, (const S *)m, (S *)y, rows_per_part, (S *)slabs, s_begin, s_end);
     else
         hipLaunchKernelGGL((k_grid_normal<S, E, NS, K, DEPTH, false>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, op->dev_blocks, op->nrow,
-                           n_scalars, (const S *)m, (S *)y, rows_per_part, (S *)slabs);
+                           n_scalars, (const S *)m, (S *)y, rows_per_part, (S *)slabs, s_begin, s_end);
     JH_CHECK_HIP(hipGetLastError());
-    if (parts > 1) return jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, (int64_t)K * n_scalars, parts, y, 0, (int64_t)K * n_scalars);
+    if (parts > 1 && !ranged) return jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, (int64_t)K * n_scalars, parts, y, 0, (int64_t)K * n_scalars);
+    if (parts > 1)                                             // (the slabs keep the whole block's stride: the range of each piece)
+        for (int k = 0; k < K; k++)
+            JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, (const S *)slabs + (int64_t)k * n_scalars + s_begin, (int64_t)K * n_scalars, parts, y,
+                                   (int64_t)k * n_scalars + s_begin, (int64_t)k * n_scalars + s_end));
     return JH_OK;
 }
 
 template <typename S, int E, int NS>
-int grid_normal_k(const jh_blockop *op, void *y, const void *m)
+int grid_normal_k(const jh_blockop *op, void *y, const void *m, int64_t first_elem, int64_t end_elem)
 {
     // rows in flight: K x DEPTH = 8 (6 for K = 3) coefficient packs per lane; 12 / 9 / 12 measured 2-3 % slower for K = 2 / 4 and within the noise for
     // K = 3 (profiles/bench_grid_normal_r06.txt)
     switch (op->ncol) {
-    case 2: return launch_grid_normal<S, E, NS, 2, 4>(op, y, m);
-    case 3: return launch_grid_normal<S, E, NS, 3, 2>(op, y, m);
-    default: return launch_grid_normal<S, E, NS, 4, 2>(op, y, m);
+    case 2: return launch_grid_normal<S, E, NS, 2, 4>(op, y, m, first_elem, end_elem);
+    case 3: return launch_grid_normal<S, E, NS, 3, 2>(op, y, m, first_elem, end_elem);
+    default: return launch_grid_normal<S, E, NS, 4, 2>(op, y, m, first_elem, end_elem);
     }
 }
 
@@ -278,16 +289,25 @@ int grid_words_ensure(const jh_blockop *op)
     return JH_OK;
 }
 
-int grid_normal(const jh_blockop *op, void *y, const void *m)
+static int grid_normal_by_dtype(const jh_blockop *op, void *y, const void *m, int64_t first_elem, int64_t end_elem)
 {
     JH_TRY(grid_words_ensure(op));                            // the packed table of a mixed grid, row-major (N x K words), built on first use
     switch (op->dtype) {
-    case JH_F32: return grid_normal_k<float, 1, 4>(op, y, m);
-    case JH_F64: return grid_normal_k<double, 1, 2>(op, y, m);
-    case JH_C32: return grid_normal_k<float, 2, 4>(op, y, m);
-    case JH_C64: return grid_normal_k<double, 2, 2>(op, y, m);
+    case JH_F32: return grid_normal_k<float, 1, 4>(op, y, m, first_elem, end_elem);
+    case JH_F64: return grid_normal_k<double, 1, 2>(op, y, m, first_elem, end_elem);
+    case JH_C32: return grid_normal_k<float, 2, 4>(op, y, m, first_elem, end_elem);
+    case JH_C64: return grid_normal_k<double, 2, 2>(op, y, m, first_elem, end_elem);
     default: return jh_fail(JH_ERR_INVALID, "grid_normal: unknown dtype %d", op->dtype);
     }
+}
+
+int grid_normal(const jh_blockop *op, void *y, const void *m) { return grid_normal_by_dtype(op, y, m, 0, -1); }
+
+// positions [first_elem, first_elem + count) of every block (jh_blockop_normal_mul_range, knob grid_range; the caller has checked grid_range_ok and
+// grid_range_bounds): the same kernels over those lanes -- the K pieces y_k[first, first + count) and nothing else
+int grid_normal_range(const jh_blockop *op, void *y, const void *m, int64_t first_elem, int64_t count)
+{
+    return grid_normal_by_dtype(op, y, m, first_elem, first_elem + count);
 }
 
 }  // namespace jhb

@@ -1,0 +1,194 @@
+// jh_grid_range.hip -- the three ranged calls that pipeline a row partition's exchange, on an N x K GRID of equal elementwise blocks, K = 2 .. 4
+// (knob grid_range = 1): jh_blockop_mul_adj_range, jh_blockop_normal_mul_range and jh_blockop_bidiag_step_range.
+//
+// A grid kernel's lane owns one pack position of the blocks across all K columns (it needs every v_k[p] for the row's forward sum), so the range of a
+// grid is [first, first + count) INSIDE a block, not a piece of the flat K n domain slab: one call reads those positions of every u_i / d_i and writes
+// the K pieces w_k[first, first + count) and nothing else.  A'A and the step are the whole-vector kernels over those lanes (k_grid_normal, k_grid_step:
+// first and last scalar are run-time arguments, the row stride stays n -- jh_grid_normal.hip, jh_grid_step.hip).  The adjoint of a grid is otherwise the
+// register-tiled general kernel (jh_general.hip: a workgroup per group of columns), which has no range; k_grid_adj below is the same lane layout as the
+// other two:
+//     m_k = ((0 + A_1k' d_1) + A_2k' d_2) + ...        columns summed from +0 in row order, zero blocks skipped (src/Jets.jl:1042-1049)
+// -- the bits of the whole-vector adjoint wherever that walks the rows in one part (-ffp-contract=off).  Many rows of small blocks take the split-row
+// walk (pick_adj_parts over the RANGE's workgroups; tolerance parity, adj_split = 0: ordered).  Blocks off the 16-byte grid: under-aligned packs, the
+// partial last pack only in the range that ends the block.
+#include "jh_grid_common.h"
+
+namespace {
+
+// MIXED: blocks of several kinds through the packed table words[i * K + k]; else plain diagonals, block (i, k) = blocks[i + k * nrow]
+template <typename S, int E, int NS, int K, int DEPTH, bool NT, bool MIXED>
+__global__ __launch_bounds__(256) void k_grid_adj(const jh_dev_block *__restrict__ blocks, const uint64_t *__restrict__ words, int64_t nrow, int64_t n_scalars,
+                                                  const S *__restrict__ d, S *__restrict__ m, int64_t rows_per_part, S *__restrict__ part_out,
+                                                  int64_t s_begin, int64_t s_end)
+{
+    typedef typename vec_of<S, NS>::type V;
+    const int64_t s0 = s_begin + ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;
+    const bool ok = s0 < s_end;
+    const int64_t sk = pack_start<NS>(ok ? s0 : s_begin, s_end);                      // (a range shorter than one pack ends with the block: loaded from s_end - NS)
+    V acc[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) acc[k] = (V)(S)0;                                     // m_k .= 0 (1042)
+    int64_t i = 0, iend = nrow;
+    if (part_out) {
+        i = (int64_t)blockIdx.y * rows_per_part;
+        iend = iend < i + rows_per_part ? iend : i + rows_per_part;
+    }
+    if constexpr (MIXED) {
+        for (; i + DEPTH <= iend; i += DEPTH) {
+            uint64_t wd[DEPTH][K];
+#pragma unroll
+            for (int j = 0; j < DEPTH; j++)
+#pragma unroll
+                for (int k = 0; k < K; k++) wd[j][k] = words[(i + j) * K + k];
+            V c[DEPTH][K], dv[DEPTH];
+#pragma unroll
+            for (int j = 0; j < DEPTH; j++) {
+#pragma unroll
+                for (int k = 0; k < K; k++)
+                    c[j][k] = gw_kind(wd[j][k]) == JH_OP_DIAG ? ldu<NT, S, NS>(reinterpret_cast<const S *>(wd[j][k] & GW_PTR) + sk) : (V)(S)0;
+                dv[j] = ldu<NT, S, NS>(d + (i + j) * n_scalars + sk);
+            }
+#pragma unroll
+            for (int j = 0; j < DEPTH; j++)
+#pragma unroll
+                for (int k = 0; k < K; k++)
+                    if (gw_kind(wd[j][k]) != JH_OP_ZERO) acc[k] = acc[k] + grid_apply<S, E, NS, V>(wd[j][k], blocks, (i + j) + (int64_t)k * nrow, dv[j], c[j][k], true);
+        }
+        for (; i < iend; i++) {
+            const V dv = ldu<NT, S, NS>(d + i * n_scalars + sk);
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const uint64_t wd = words[i * K + k];
+                const V c = gw_kind(wd) == JH_OP_DIAG ? ldu<NT, S, NS>(reinterpret_cast<const S *>(wd & GW_PTR) + sk) : (V)(S)0;
+                if (gw_kind(wd) != JH_OP_ZERO) acc[k] = acc[k] + grid_apply<S, E, NS, V>(wd, blocks, i + (int64_t)k * nrow, dv, c, true);
+            }
+        }
+    } else {
+        // the next batch's pointers are requested while this batch's packs are in flight (k_grid_normal)
+        const S *nxt[DEPTH][K];
+#pragma unroll
+        for (int j = 0; j < DEPTH; j++)
+#pragma unroll
+            for (int k = 0; k < K; k++) nxt[j][k] = (const S *)blocks[(i + j < iend ? i + j : i) + (int64_t)k * nrow].coeff;
+        for (; i + DEPTH <= iend; i += DEPTH) {
+            const S *a[DEPTH][K];
+#pragma unroll
+            for (int j = 0; j < DEPTH; j++)
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    a[j][k] = nxt[j][k];
+                    const int64_t r = i + DEPTH + j;
+                    nxt[j][k] = (const S *)blocks[(r < iend ? r : i) + (int64_t)k * nrow].coeff;
+                }
+            V c[DEPTH][K], dv[DEPTH];
+#pragma unroll
+            for (int j = 0; j < DEPTH; j++) {
+#pragma unroll
+                for (int k = 0; k < K; k++) c[j][k] = ldu<NT, S, NS>(a[j][k] + sk);
+                dv[j] = ldu<NT, S, NS>(d + (i + j) * n_scalars + sk);
+            }
+#pragma unroll
+            for (int j = 0; j < DEPTH; j++)
+#pragma unroll
+                for (int k = 0; k < K; k++) acc[k] = acc[k] + vmul<S, E, NS, V>(c[j][k], dv[j], true);   // m_k .+= A_ik' d_i (1049)
+        }
+        for (; i < iend; i++) {
+            const V dv = ldu<NT, S, NS>(d + i * n_scalars + sk);
+#pragma unroll
+            for (int k = 0; k < K; k++) acc[k] = acc[k] + vmul<S, E, NS, V>(ldu<NT, S, NS>((const S *)blocks[i + (int64_t)k * nrow].coeff + sk), dv, true);
+        }
+    }
+    if (!ok) return;
+    S *o = part_out ? part_out + (int64_t)blockIdx.y * (K * n_scalars) : m;
+#pragma unroll
+    for (int k = 0; k < K; k++) st_pack<false, S, NS>(o + (int64_t)k * n_scalars, s0, sk, acc[k]);
+}
+
+template <typename S, int E, int NS, int K, int DEPTH>
+int launch_grid_adj(const jh_blockop *op, void *m, const void *d, int64_t first_elem, int64_t end_elem)
+{
+    jh_context &c = jh_ctx();
+    const int64_t n_scalars = op->row_len[0] * E, s_begin = first_elem * E, s_end = end_elem * E;
+    const int64_t packs = (s_end - s_begin + NS - 1) / NS;
+    const int64_t gx = (packs + 255) / 256;
+    // the part rules of launch_grid_normal, over the range's workgroups (a range shorter than one pack loads from before s_begin: one part)
+    int64_t parts = s_end - s_begin < NS ? 1 : jhb::pick_adj_parts(gx, op->nrow), rows_per_part = 0;
+    if (parts == 1 && s_end - s_begin >= NS && c.adj_split < 0 && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
+    void *slabs = nullptr;
+    if (parts > 1) {
+        rows_per_part = (op->nrow + parts - 1) / parts;
+        parts = (op->nrow + rows_per_part - 1) / rows_per_part;
+        JH_TRY(jhb::split_slabs(m, (size_t)parts * (size_t)K * (size_t)n_scalars * sizeof(S), &slabs));
+    }
+    c.last_adj_parts = parts;
+    c.last_adj_launches = 1;
+    // streamed once per pass: the coefficients and d -- over the WHOLE adjoint's bytes, so that a range streams like the whole vector would
+    const bool nt = jh_stream_nt(((double)K + 1.0) * (double)op->nrow * (double)n_scalars * sizeof(S));
+    c.last_grid_range_shape = (nt ? 1 : 0) | (parts > 1 ? 2 : 0);
+#define JH_GRID_ADJ(NTV, MIX)                                                                                                                      \
+    hipLaunchKernelGGL((k_grid_adj<S, E, NS, K, DEPTH, NTV, MIX>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, op->dev_blocks,    \
+                       (const uint64_t *)op->grid_words, op->nrow, n_scalars, (const S *)d, (S *)m, rows_per_part, (S *)slabs, s_begin, s_end)
+    if (!op->all_diag) {
+        if (nt) JH_GRID_ADJ(true, true);
+        else JH_GRID_ADJ(false, true);
+    } else {
+        if (nt) JH_GRID_ADJ(true, false);
+        else JH_GRID_ADJ(false, false);
+    }
+#undef JH_GRID_ADJ
+    JH_CHECK_HIP(hipGetLastError());
+    if (parts > 1)                                             // (the slabs keep the whole block's stride: the range of each piece)
+        for (int k = 0; k < K; k++)
+            JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, (const S *)slabs + (int64_t)k * n_scalars + s_begin, (int64_t)K * n_scalars, parts, m,
+                                   (int64_t)k * n_scalars + s_begin, (int64_t)k * n_scalars + s_end));
+    return JH_OK;
+}
+
+template <typename S, int E, int NS>
+int grid_adj_k(const jh_blockop *op, void *m, const void *d, int64_t first_elem, int64_t end_elem)
+{
+    // rows in flight: the depths of k_grid_normal -- K x DEPTH = 8 (6 for K = 3) coefficient packs per lane, plus DEPTH packs of d
+    switch (op->ncol) {
+    case 2: return launch_grid_adj<S, E, NS, 2, 4>(op, m, d, first_elem, end_elem);
+    case 3: return launch_grid_adj<S, E, NS, 3, 2>(op, m, d, first_elem, end_elem);
+    default: return launch_grid_adj<S, E, NS, 4, 2>(op, m, d, first_elem, end_elem);
+    }
+}
+
+}  // namespace
+
+namespace jhb {
+
+// the grids of the whole-vector one-pass kernels (grid_shape_ok: N >= 2, K = 2 .. 4, equal elementwise blocks of >= 16 bytes, no nonlinear child), the
+// knob, and vectors aligned like their scalar (c may be NULL)
+bool grid_range_ok(const jh_blockop *op, const void *a, const void *b, const void *c)
+{
+    if (jh_ctx().grid_range != 1 || !grid_shape_ok(op, true)) return false;
+    const size_t es = jh_dtype_size(op->dtype), sa = jh_dtype_complex(op->dtype) ? es / 2 : es;
+    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & (sa - 1)) == 0;
+}
+
+int grid_range_bounds(const jh_blockop *op, int64_t first_elem, int64_t count, const char *who)
+{
+    const int64_t n = op->row_len[0], es = (int64_t)jh_dtype_size(op->dtype);
+    JH_REQUIRE(first_elem >= 0 && count >= 0 && first_elem + count <= n,
+               "%s: on an N x K grid the range is positions inside a block: [%lld, %lld) is outside a block of %lld elements", who, (long long)first_elem,
+               (long long)(first_elem + count), (long long)n);
+    JH_REQUIRE((first_elem * es) % 16 == 0 && ((count * es) % 16 == 0 || first_elem + count == n),
+               "%s: range boundaries must be 16-byte aligned inside the block (the last range may end with the block)", who);
+    return JH_OK;
+}
+
+int grid_adj_range(const jh_blockop *op, void *m, const void *d, int64_t first_elem, int64_t count)
+{
+    JH_TRY(grid_words_ensure(op));
+    switch (op->dtype) {
+    case JH_F32: return grid_adj_k<float, 1, 4>(op, m, d, first_elem, first_elem + count);
+    case JH_F64: return grid_adj_k<double, 1, 2>(op, m, d, first_elem, first_elem + count);
+    case JH_C32: return grid_adj_k<float, 2, 4>(op, m, d, first_elem, first_elem + count);
+    case JH_C64: return grid_adj_k<double, 2, 2>(op, m, d, first_elem, first_elem + count);
+    default: return jh_fail(JH_ERR_INVALID, "grid adjoint: unknown dtype %d", op->dtype);
+    }
+}
+
+}  // namespace jhb

@@ -34,15 +34,17 @@ __device__ inline V grid_u_update(S *urow, int64_t s0, int64_t sk, int e0, bool 
 // MIXED: blocks of several kinds through the packed table words[i * K + k]; else plain diagonals, block (i, k) = blocks[i + k * nrow].
 // OLD: beta != 0 -- u is read; else it is write-only.  (Decided at compile time: with the choice made per row, as in the tall plain walk, the
 // walks of K = 2 .. 4 spilled 2-15 SGPRs.)
+// The lanes cover the scalars [s_begin, s_end) of a block (the whole block: 0, n_scalars; a range of it: jh_blockop_bidiag_step_range with the knob
+// grid_range); n_scalars stays the stride of the rows of u and of the pieces of v, w and the parts' slabs.
 template <typename S, int E, int NS, int K, int DEPTH, bool NT, bool MIXED, bool OLD>
 __global__ __launch_bounds__(256) void k_grid_step(const jh_dev_block *__restrict__ blocks, const uint64_t *__restrict__ words, int64_t nrow, int64_t n_scalars,
                                                    S *__restrict__ u, const S *__restrict__ v, S *__restrict__ w, S alpha, S beta,
-                                                   double *__restrict__ partials, int64_t rows_per_part, S *__restrict__ part_out)
+                                                   double *__restrict__ partials, int64_t rows_per_part, S *__restrict__ part_out, int64_t s_begin, int64_t s_end)
 {
     typedef typename vec_of<S, NS>::type V;
-    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;
-    const bool ok = s0 < n_scalars;
-    const int64_t sk = pack_start<NS>(ok ? s0 : 0, n_scalars);
+    const int64_t s0 = s_begin + ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;
+    const bool ok = s0 < s_end;
+    const int64_t sk = pack_start<NS>(ok ? s0 : s_begin, s_end);                      // (a range shorter than one pack ends with the block: loaded from s_end - NS)
     const int e0 = ok ? (int)(s0 - sk) : 0;                                         // a row's partial last pack counts the scalars it OWNS
     V x[K], acc[K];
 #pragma unroll
@@ -56,6 +58,9 @@ __global__ __launch_bounds__(256) void k_grid_step(const jh_dev_block *__restric
         iend = iend < i + rows_per_part ? iend : i + rows_per_part;
     }
     double nrm = 0.0;
+    // (alpha and beta in vector registers, as in k_grid_chain_step: with the range's two bounds among the arguments one walk spilled 2 SGPRs otherwise)
+    S av = alpha, bv = beta;
+    asm volatile("" : "+v"(av), "+v"(bv));
     if constexpr (MIXED) {
         // (the words of a batch are read when the batch starts, not one batch ahead as in k_grid_normal_mixed: the SGPRs of the records in flight
         // plus u's row are what made this walk spill -- DESIGN 3.8b, the grid chain's lesson)
@@ -83,7 +88,7 @@ __global__ __launch_bounds__(256) void k_grid_step(const jh_dev_block *__restric
                     V t = (V)(S)0;
 #pragma unroll
                     for (int k = 0; k < K; k++) t = t + vmul<S, E, NS, V>(c[j][k], x[k], false);
-                    const V r = grid_u_update<NT, OLD, S, NS, V>(u + (i + j) * n_scalars, s0, sk, e0, ok, t, uo[j], alpha, beta, nrm);
+                    const V r = grid_u_update<NT, OLD, S, NS, V>(u + (i + j) * n_scalars, s0, sk, e0, ok, t, uo[j], av, bv, nrm);
 #pragma unroll
                     for (int k = 0; k < K; k++) acc[k] = acc[k] + vmul<S, E, NS, V>(c[j][k], r, true);
                 }
@@ -95,7 +100,7 @@ __global__ __launch_bounds__(256) void k_grid_step(const jh_dev_block *__restric
 #pragma unroll
                 for (int k = 0; k < K; k++)
                     if (gw_kind(wd[j][k]) != JH_OP_ZERO) t = t + grid_apply<S, E, NS, V>(wd[j][k], blocks, (i + j) + (int64_t)k * nrow, x[k], c[j][k], false);
-                const V r = grid_u_update<NT, OLD, S, NS, V>(u + (i + j) * n_scalars, s0, sk, e0, ok, t, uo[j], alpha, beta, nrm);
+                const V r = grid_u_update<NT, OLD, S, NS, V>(u + (i + j) * n_scalars, s0, sk, e0, ok, t, uo[j], av, bv, nrm);
 #pragma unroll
                 for (int k = 0; k < K; k++)
                     if (gw_kind(wd[j][k]) != JH_OP_ZERO) acc[k] = acc[k] + grid_apply<S, E, NS, V>(wd[j][k], blocks, (i + j) + (int64_t)k * nrow, r, c[j][k], true);
@@ -114,7 +119,7 @@ __global__ __launch_bounds__(256) void k_grid_step(const jh_dev_block *__restric
 #pragma unroll
             for (int k = 0; k < K; k++)
                 if (gw_kind(wd[k]) != JH_OP_ZERO) t = t + grid_apply<S, E, NS, V>(wd[k], blocks, i + (int64_t)k * nrow, x[k], c[k], false);
-            const V r = grid_u_update<NT, OLD, S, NS, V>(u + i * n_scalars, s0, sk, e0, ok, t, uo, alpha, beta, nrm);
+            const V r = grid_u_update<NT, OLD, S, NS, V>(u + i * n_scalars, s0, sk, e0, ok, t, uo, av, bv, nrm);
 #pragma unroll
             for (int k = 0; k < K; k++)
                 if (gw_kind(wd[k]) != JH_OP_ZERO) acc[k] = acc[k] + grid_apply<S, E, NS, V>(wd[k], blocks, i + (int64_t)k * nrow, r, c[k], true);
@@ -148,7 +153,7 @@ __global__ __launch_bounds__(256) void k_grid_step(const jh_dev_block *__restric
                 V t = (V)(S)0;                                                      // zeros(range(A)) (531)
 #pragma unroll
                 for (int k = 0; k < K; k++) t = t + vmul<S, E, NS, V>(c[j][k], x[k], false);     // d_i .+= A_ik v_k (1024)
-                const V r = grid_u_update<NT, OLD, S, NS, V>(u + (i + j) * n_scalars, s0, sk, e0, ok, t, uo[j], alpha, beta, nrm);
+                const V r = grid_u_update<NT, OLD, S, NS, V>(u + (i + j) * n_scalars, s0, sk, e0, ok, t, uo[j], av, bv, nrm);
 #pragma unroll
                 for (int k = 0; k < K; k++) acc[k] = acc[k] + vmul<S, E, NS, V>(c[j][k], r, true);  // m_k .+= A_ik' u_i (1049)
             }
@@ -161,7 +166,7 @@ __global__ __launch_bounds__(256) void k_grid_step(const jh_dev_block *__restric
             V t = (V)(S)0;
 #pragma unroll
             for (int k = 0; k < K; k++) t = t + vmul<S, E, NS, V>(c[k], x[k], false);
-            const V r = grid_u_update<NT, OLD, S, NS, V>(u + i * n_scalars, s0, sk, e0, ok, t, uo, alpha, beta, nrm);
+            const V r = grid_u_update<NT, OLD, S, NS, V>(u + i * n_scalars, s0, sk, e0, ok, t, uo, av, bv, nrm);
 #pragma unroll
             for (int k = 0; k < K; k++) acc[k] = acc[k] + vmul<S, E, NS, V>(c[k], r, true);
         }
@@ -175,13 +180,18 @@ __global__ __launch_bounds__(256) void k_grid_step(const jh_dev_block *__restric
 }
 
 template <typename S, int E, int NS, int K, int DEPTH, int MDEPTH>
-int launch_grid_step(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq)
+int launch_grid_step(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq, int64_t first_elem, int64_t end_elem)
 {
     jh_context &c = jh_ctx();
-    const int64_t n_scalars = op->row_len[0] * E, packs = (n_scalars + NS - 1) / NS;
+    // end_elem < 0: the whole block; else the positions [first_elem, end_elem) of every block, launched as a vector of its own length, ||u||^2 deferred
+    // (the split walk's slabs keep the whole block's stride for a range too -- parts x K x n_scalars, of which a range touches its share: the kernel then
+    // needs no second stride; the split walk is the regime of small blocks, where that is little memory)
+    const bool ranged = end_elem >= 0;
+    const int64_t n_scalars = op->row_len[0] * E, s_begin = ranged ? first_elem * E : 0, s_end = ranged ? end_elem * E : n_scalars;
+    const int64_t packs = (s_end - s_begin + NS - 1) / NS;
     const int64_t gx = (packs + 255) / 256;
-    int64_t parts = jhb::pick_adj_parts(gx, op->nrow), rows_per_part = 0;
-    if (parts == 1 && c.adj_split < 0 && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;   // (as launch_grid_normal)
+    int64_t parts = s_end - s_begin < NS ? 1 : jhb::pick_adj_parts(gx, op->nrow), rows_per_part = 0;   // (a range shorter than one pack loads from before s_begin: one part)
+    if (parts == 1 && s_end - s_begin >= NS && c.adj_split < 0 && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;   // (as launch_grid_normal)
     void *slabs = nullptr;
     if (parts > 1) {
         rows_per_part = (op->nrow + parts - 1) / parts;
@@ -193,12 +203,12 @@ int launch_grid_step(const jh_blockop *op, void *u, const void *v, void *w, doub
     const bool nt = jh_stream_nt(((double)K + (beta != 0.0 ? 2.0 : 1.0)) * (double)op->nrow * (double)n_scalars * sizeof(S));
     c.last_adj_parts = parts;
     c.last_adj_launches = 1;
-    c.last_grid_step_shape = (nt ? 1 : 0) | (parts > 1 ? 2 : 0);
+    (ranged ? c.last_grid_range_shape : c.last_grid_step_shape) = (nt ? 1 : 0) | (parts > 1 ? 2 : 0);
     const bool mixed = !op->all_diag;
 #define JH_GRID_STEP(NTV, MIX, OLDV)                                                                                                         \
     hipLaunchKernelGGL((k_grid_step<S, E, NS, K, MIX ? MDEPTH : DEPTH, NTV, MIX, OLDV>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, \
                        op->dev_blocks, (const uint64_t *)op->grid_words, op->nrow, n_scalars, (S *)u, (const S *)v, (S *)w, (S)alpha, (S)beta,    \
-                       c.part_dev, rows_per_part, (S *)slabs)
+                       c.part_dev, rows_per_part, (S *)slabs, s_begin, s_end)
 #define JH_GRID_STEP_OLD(NTV, MIX)         \
     if (beta != 0.0) JH_GRID_STEP(NTV, MIX, true); \
     else JH_GRID_STEP(NTV, MIX, false)
@@ -212,21 +222,25 @@ int launch_grid_step(const jh_blockop *op, void *u, const void *v, void *w, doub
 #undef JH_GRID_STEP_OLD
 #undef JH_GRID_STEP
     JH_CHECK_HIP(hipGetLastError());
-    if (parts > 1) JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, (int64_t)K * n_scalars, parts, w, 0, (int64_t)K * n_scalars));
-    return jhb::step_finish_normsq(gx * parts, normsq);
+    if (parts > 1 && !ranged) JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, (int64_t)K * n_scalars, parts, w, 0, (int64_t)K * n_scalars));
+    if (parts > 1 && ranged)                                                        // (the slabs keep the whole block's stride: the range of each piece)
+        for (int k = 0; k < K; k++)
+            JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, (const S *)slabs + (int64_t)k * n_scalars + s_begin, (int64_t)K * n_scalars, parts, w,
+                                   (int64_t)k * n_scalars + s_begin, (int64_t)k * n_scalars + s_end));
+    return jhb::step_finish_normsq(gx * parts, normsq, ranged);
 }
 
 template <typename S, int E, int NS>
-int grid_step_k(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq)
+int grid_step_k(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq, int64_t first_elem, int64_t end_elem)
 {
     // rows in flight: plain diagonals keep the depths of k_grid_normal -- K x DEPTH = 8 (6 for K = 3) coefficient packs per lane, plus DEPTH packs
     // of u; grids of several kinds half of that for K = 2 and 4 (MDEPTH): at the plain depths their walk spills SGPRs (the block words, the scalars).
     // ComplexF32 (the longest product code) also takes one row at a time for K = 3 of several kinds and K = 4 of plain diagonals: 2 SGPRs spilled otherwise
     constexpr bool c32 = E == 2 && sizeof(S) == 4;
     switch (op->ncol) {
-    case 2: return launch_grid_step<S, E, NS, 2, 4, 2>(op, u, v, w, alpha, beta, normsq);
-    case 3: return launch_grid_step<S, E, NS, 3, 2, c32 ? 1 : 2>(op, u, v, w, alpha, beta, normsq);
-    default: return launch_grid_step<S, E, NS, 4, c32 ? 1 : 2, 1>(op, u, v, w, alpha, beta, normsq);
+    case 2: return launch_grid_step<S, E, NS, 2, 4, 2>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
+    case 3: return launch_grid_step<S, E, NS, 3, 2, c32 ? 1 : 2>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
+    default: return launch_grid_step<S, E, NS, 4, c32 ? 1 : 2, 1>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
     }
 }
 
@@ -242,16 +256,29 @@ bool grid_step_ok(const jh_blockop *op, const void *u, const void *v, const void
 }
 
 // the caller has checked grid_step_ok; w must not alias v (jh_blockop_bidiag_step)
-int grid_step(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq)
+static int grid_step_by_dtype(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq, int64_t first_elem, int64_t end_elem)
 {
     JH_TRY(grid_words_ensure(op));
     switch (op->dtype) {
-    case JH_F32: return grid_step_k<float, 1, 4>(op, u, v, w, alpha, beta, normsq);
-    case JH_F64: return grid_step_k<double, 1, 2>(op, u, v, w, alpha, beta, normsq);
-    case JH_C32: return grid_step_k<float, 2, 4>(op, u, v, w, alpha, beta, normsq);
-    case JH_C64: return grid_step_k<double, 2, 2>(op, u, v, w, alpha, beta, normsq);
+    case JH_F32: return grid_step_k<float, 1, 4>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
+    case JH_F64: return grid_step_k<double, 1, 2>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
+    case JH_C32: return grid_step_k<float, 2, 4>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
+    case JH_C64: return grid_step_k<double, 2, 2>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
     default: return jh_fail(JH_ERR_INVALID, "grid step: unknown dtype %d", op->dtype);
     }
+}
+
+int grid_step(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq)
+{
+    return grid_step_by_dtype(op, u, v, w, alpha, beta, normsq, 0, -1);
+}
+
+// positions [first_elem, first_elem + count) of every block (jh_blockop_bidiag_step_range, knob grid_range; the caller has checked grid_range_ok and
+// grid_range_bounds): the same kernel over those lanes.  The nontemporal rule sees the WHOLE step's bytes, so a ranged step streams like the whole one;
+// the range's share of ||u||^2 is returned, or (normsq == NULL) added to the context's accumulator in enqueue order.
+int grid_step_range(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, int64_t first_elem, int64_t count, double *normsq)
+{
+    return grid_step_by_dtype(op, u, v, w, alpha, beta, normsq, first_elem, first_elem + count);
 }
 
 }  // namespace jhb

@@ -147,6 +147,8 @@ struct jh_context {
     int64_t last_grid_step_shape = 0;  // how the most recent grid step was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
     int64_t grid_chain_step = 0;       // knob: jh_chain_bidiag_step (and the LSQR / CGLS loops of jh_lsqr_solve_chain / jh_cgls_solve_chain) on a FORWARD chain through an N x (2 .. 4) grid in one pass (jh_grid_chain_step.hip): 1 yes, 0 (default) JH_ERR_UNSUPPORTED as before
     int64_t last_grid_chain_step_shape = 0;   // how the most recent grid chain step was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
+    int64_t grid_range = 0;            // knob: jh_blockop_mul_adj_range / _normal_mul_range / _bidiag_step_range on an N x (2 .. 4) grid of equal elementwise blocks, the range being positions INSIDE a block (jh_grid_range.hip): 1 yes, 0 (default) JH_ERR_UNSUPPORTED as before
+    int64_t last_grid_range_shape = 0; // how the most recent ranged grid call was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
     int64_t fwd_anchor = -1;           // knob: the tall forward of rows that are not whole packs on lanes anchored to each row's own 16-byte grid (k_tall_fwd_anchored): -1 from 64 KiB rows on, 0 never, 1 always
     int64_t wide_twin = 1;             // knob: wide elementwise operators on their tall twin: 0 never (general kernels), 1 adjoint always + forward from 16 MiB blocks, 2 both always (tests)
     const double *step_coef_dev = nullptr;   // internal, set around the calls of the graph-captured LSQR loop: the one-pass step reads (alpha, beta) from
@@ -174,6 +176,13 @@ namespace jhb { bool grid_normal_ok(const jh_blockop *op, const void *y, const v
 namespace jhb {   // jh_grid_step.hip: the one-pass Golub-Kahan step of an N x (2 .. 4) grid of equal elementwise blocks (knob grid_step; vectors aligned like their scalar)
 bool grid_step_ok(const jh_blockop *op, const void *u, const void *v, const void *w);
 int grid_step(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq);
+}
+namespace jhb {   // the three ranged calls on an N x (2 .. 4) grid (knob grid_range): positions [first, first + count) of every block (jh_grid_range.hip: the checks and the adjoint; jh_grid_normal.hip, jh_grid_step.hip: their kernels over a range)
+bool grid_range_ok(const jh_blockop *op, const void *a, const void *b, const void *c);   // the knob, the grid's shape, vectors aligned like their scalar
+int grid_range_bounds(const jh_blockop *op, int64_t first_elem, int64_t count, const char *who);   // inside a block, on the 16-byte grid (the last range may end with the block)
+int grid_adj_range(const jh_blockop *op, void *m, const void *d, int64_t first_elem, int64_t count);
+int grid_normal_range(const jh_blockop *op, void *y, const void *m, int64_t first_elem, int64_t count);
+int grid_step_range(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, int64_t first_elem, int64_t count, double *normsq);
 }
 namespace jhb {   // jh_grid_chain_step.hip: the one-pass Golub-Kahan step of a FORWARD chain through an N x (2 .. 4) grid (knob grid_chain_step; the checks are jh_chain_bidiag_step's)
 int grid_chain_step(const jh_chain *ch, void *u, const void *v, void *w, double alpha, double beta, double *normsq);

@@ -1061,8 +1061,19 @@ int jh_blockop_bidiag_step_range(const jh_blockop *op, jh_bvec *u, const jh_bvec
                "jh_blockop_bidiag_step_range: elements [%lld, %lld) outside the domain vector (%lld elements)", (long long)first_elem,
                (long long)(first_elem + count), (long long)v->length);
     // (rows off the 16-byte pack grid: the plain walk's MIXED instantiations, like the whole-vector call -- the LAST range may then end inside a pack)
-    if (!jh_blockop_tall_step_ok(op, u->data, v->data) || (((uintptr_t)w->data) & (jh_dtype_size(op->dtype) / (jh_dtype_complex(op->dtype) ? 2 : 1) - 1)))
+    if (!jh_blockop_tall_step_ok(op, u->data, v->data) || (((uintptr_t)w->data) & (jh_dtype_size(op->dtype) / (jh_dtype_complex(op->dtype) ? 2 : 1) - 1))) {
+        // an N x (2 .. 4) grid of equal elementwise blocks (knob grid_range = 1): the range is positions INSIDE a block (jh_grid_step.hip)
+        // (and the whole-vector step's own knob: with grid_step = 0 the ranged step declines what jh_blockop_bidiag_step declines)
+        if (jhb::grid_range_ok(op, u->data, v->data, w->data) && jhb::grid_step_ok(op, u->data, v->data, w->data)) {
+            JH_TRY(jhb::grid_range_bounds(op, first_elem, count, "jh_blockop_bidiag_step_range"));
+            if (count == 0) {
+                if (normsq) *normsq = 0.0;
+                return JH_OK;
+            }
+            return jhb::grid_step_range(op, u->data, v->data, w->data, alpha, beta, first_elem, count, normsq);
+        }
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_blockop_bidiag_step_range: needs a tall operator of >= 2 equal elementwise rows");
+    }
     const int64_t es = (int64_t)jh_dtype_size(op->dtype);
     JH_REQUIRE((first_elem * es) % 16 == 0 && ((count * es) % 16 == 0 || first_elem + count == v->length),
                "jh_blockop_bidiag_step_range: chunk boundaries must be 16-byte aligned (the last chunk may end with the vector)");

@@ -250,11 +250,38 @@ class _ShardEngine(_Engine):
         # a weighted shard under an exchange: the one-pass chain step range by range (rowpart: jh_chain_bidiag_step_range), no range temporary --
         # LSQR every iteration, the warm start, CGLS's second pass (cgls.cgls_core).  JETS_CHAIN_STEP=0: the chain into a range temporary, as before.
         self.chain_step = bool(getattr(shard, "chain_step", False)) and (shard.comm.world > 1 or self.force_collective)
+        # a shard whose local operator is an N x (2 .. 4) grid, under an exchange with the knob grid_range = 1: the grid's one-pass step and its fused A'A
+        # range by range (rowpart: jh_blockop_bidiag_step_range / _normal_mul_range over positions inside a block), no range temporary -- LSQR every
+        # iteration, CGNR's normal operator, CGLS's second pass; CGLS's first pass is the local fused A'A and one scalar (normal_cgls)
+        self.grid_range = bool(getattr(shard, "grid_range", False)) and (shard.comm.world > 1 or self.force_collective)
+        if self.grid_range:
+            self.normal = self._normal
+            self.normal_cgls = self._normal_local
+
+    def _normal_local(self, y, p) -> float:
+        """<p, A'A p> over all ranks without exchanging a vector: this rank's fused A_loc'A_loc p (jh_blockop_normal_mul on the grid) and ONE scalar
+        all-reduce.  None when the library declines the fused A'A (cgls_core then takes the textbook passes)."""
+        nat = _blk._grid_native(self.A)
+        try:
+            check(lib.jh_blockop_normal_mul(nat.handle, y.handle, p.handle))
+        except JetsHipError as e:
+            if e.status != 4:
+                raise
+            return None
+        v = dot(p, y)
+        return self.shard.comm.all_reduce_scalars([float(getattr(v, "real", v))], "sum")[0]
 
     def _normal(self, y, p) -> float:
         """y = L'L p summed over the ranks (rowpart: normal_mul_, one fused pass + the ranged all-reduces); returns <p, y>, taken on the
         replicated domain vector (every rank the same value)."""
-        self.shard.normal_mul_(y, p, force_collective=self.force_collective)
+        if not self.shard.fused_normal_mul_(y, p, force_collective=self.force_collective):
+            # (a grid shard whose ranged A'A the library declined before anything was enqueued -- blocks it has no grid kernel for, one exchange range,
+            # the knob back at 0: A then A' through a range vector, what cgnr_core does without the hook)
+            if self._tmp_q is None:
+                self._tmp_q = zeros(_j.range_(self.A))
+            qn = self.fwd(self._tmp_q, p, 1.0, 0.0)
+            self.adj(y, self._tmp_q, 1.0, 0.0)
+            return qn * qn
         v = dot(p, y)
         return float(getattr(v, "real", v))
 
@@ -264,7 +291,7 @@ class _ShardEngine(_Engine):
     @property
     def step_cgls(self) -> bool:
         """cgls_core takes its two-pass form: <p, L'L p> through `normal`, then r <- r - alpha L p, ||r|| and L'r in one ranged chain step."""
-        return self.chain_step and self.fused_step and getattr(self, "normal", None) is not None
+        return (self.chain_step or self.grid_range) and self.fused_step and getattr(self, "normal", None) is not None
 
     def fwd(self, u, v, alpha, beta) -> float:
         if self.chain_step and self.fused_step:          # a chain has no forward-with-axpby: one step into the scratch domain vector (the warm start)
@@ -274,13 +301,13 @@ class _ShardEngine(_Engine):
         return math.sqrt(self.shard.comm.all_reduce_scalars([self._fwd_local(u, v, alpha, beta)], "sum")[0])
 
     def step(self, u, v, alpha, beta):
-        if (self.native is not None or self.chain_step) and self.fused_step:  # pipelined: all-reduce of a finished chunk of A'u under the next chunk's kernel
+        if (self.native is not None or self.chain_step or self.grid_range) and self.fused_step:  # pipelined: all-reduce of a finished chunk of A'u under the next chunk's kernel
             if self._tmp_d is None:
                 self._tmp_d = zeros(_j.domain(self.A))
             nrm2 = self.shard.bidiag_step_(u, v, self._tmp_d, alpha, beta, force_collective=self.force_collective)
             if nrm2 is not None:
                 return math.sqrt(nrm2), self._tmp_d
-            self.chain_step = False                      # (a weighted shard whose step the library declined: the two halves from here on)
+            self.chain_step = self.grid_range = False    # (a weighted or grid shard whose step the library declined: the two halves from here on)
         r = self._step_local(u, v, alpha, beta)          # this rank's rows: local ||u||^2 and local A'u
         if r is None:
             return None

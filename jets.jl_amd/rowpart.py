@@ -153,8 +153,9 @@ class RowPartitionedOp:
     def __init__(self, part: RowPartition, local_op, comm: Comm, local_mul: Callable, local_mul_adj: Callable,
                  local_dot: Callable, local_norm: Callable, pipelined_adj: Callable | None = None,
                  pipelined_step: Callable | None = None, pipelined_normal: Callable | None = None,
-                 local_normal: Callable | None = None, chains=None):
+                 local_normal: Callable | None = None, chains=None, grid_n: int | None = None):
         self.part, self.local_op, self.comm = part, local_op, comm
+        self._grid_n = grid_n                  # the block length when local_op is an N x (2 .. 4) grid of equal blocks (its ranges are cut over it), else None
         self._mul, self._mul_adj, self._dot, self._norm = local_mul, local_mul_adj, local_dot, local_norm
         self._pipelined_adj = pipelined_adj   # optional: local adjoint and all-reduce pipelined chunk by chunk
         self._pipelined_step = pipelined_step  # optional: one-pass Golub-Kahan step, its w all-reduced chunk by chunk; returns the global ||u||^2
@@ -172,6 +173,12 @@ class RowPartitionedOp:
         """bidiag_step_ runs a weighted shard's one-pass chain step range by range (jh_chain_bidiag_step_range): no range temporary."""
         return self._chains is not None and self._chains.has_step and self._pipelined_step is not None
 
+    @property
+    def grid_range(self) -> bool:
+        """The local operator is an N x (2 .. 4) grid whose adjoint, A'A and one-pass step run range by range (knob grid_range = 1): the
+        ranges are cut over the block length, a finished range's K pieces are exchanged under the next range's kernel."""
+        return self._pipelined_step is not None and self._grid_n is not None and _grid_range_on()
+
     def close(self):
         """Release the chain handles of a weighted shard (the operator itself stays the caller's)."""
         if self._chains is not None:
@@ -184,16 +191,25 @@ class RowPartitionedOp:
         fused kernel run forward then adjoint through `tmp_local` (a range vector of this rank's rows).  A weighted shard (L = W_loc o A_loc,
         a * (W o A), W o A o M: one fused run of the chain planner) runs L'L = A'W'WA as ONE NORMAL chain per range (jh_chain_apply_range), exchanged
         the same way -- or, unpipelined, the whole-vector NORMAL chain and one all-reduce; it needs no `tmp_local`."""
-        if self._pipelined_normal is not None and (self.comm.world > 1 or force_collective):
-            if self._pipelined_normal(y, self.local_op, m):
-                return y
-        if tmp_local is None and self._local_normal is not None:
-            self._local_normal(y, self.local_op, m)
-            return self.comm.all_reduce_sum_(y, force=force_collective)
+        if self.fused_normal_mul_(y, m, force_collective=force_collective, pipelined_only=tmp_local is not None):
+            return y
         if tmp_local is None:
             raise ValueError("normal_mul_: this operator has no fused A'A; pass tmp_local (a range vector of this rank's rows)")
         self.mul_(tmp_local, m)
         return self.mul_adj_(y, tmp_local, force_collective=force_collective)
+
+    def fused_normal_mul_(self, y, m, force_collective: bool = False, pipelined_only: bool = False) -> bool:
+        """normal_mul_ where it needs no range temporary: the ranged fused A'A (or NORMAL chain) with its pipelined exchange, else a weighted
+        shard's whole-vector NORMAL chain and one all-reduce.  False -- nothing enqueued, y untouched -- when the operator has neither, or the
+        library declines the ranged call on its first range: the caller then applies A and A' through a range vector."""
+        if self._pipelined_normal is not None and (self.comm.world > 1 or force_collective):
+            if self._pipelined_normal(y, self.local_op, m):
+                return True
+        if pipelined_only or self._local_normal is None:
+            return False
+        self._local_normal(y, self.local_op, m)
+        self.comm.all_reduce_sum_(y, force=force_collective)
+        return True
 
     def bidiag_step_(self, u_local, v, w, alpha: float, beta: float, force_collective: bool = False):
         """u_local <- alpha*(A_local v) + beta*u_local ; w <- sum over ALL ranks of A_local' u_local, the all-reduce of a
@@ -302,7 +318,7 @@ def for_device(part: RowPartition, local_op, comm=None) -> RowPartitionedOp:
     sc = _ShardChains(local_op)
     routes = {} if xch is None else _pipelined_routes(xch, local_op, sc)
     return RowPartitionedOp(part, local_op, comm, lambda d, A, m: mul_(d, A, m), lambda m, A, d: mul_(m, adjoint(A), d), dot, norm,
-                            local_normal=sc.local_normal if sc.has_normal else None, chains=sc, **routes)
+                            local_normal=sc.local_normal if sc.has_normal else None, chains=sc, grid_n=_grid_block_len(local_op), **routes)
 
 
 class _TorchExchange:
@@ -388,18 +404,63 @@ class _AbiExchange:
         return out.value
 
 
-def _pipelined(xch, out, nchunks: int, kernel, finish=None):
+def _grid_range_on() -> bool:
+    """Does the library take the ranged calls of a grid in the CURRENT context (knob grid_range; the default is 0)?"""
+    from .device import tune_get
+
+    return tune_get("grid_range") == 1
+
+
+def _grid_block_len(A):
+    """The block length n of a device-native N x (2 .. 4) grid of equal blocks, else None: a property of the operator, worked out once where
+    the routes are built (it walks the N K children).  Whether the ranged calls take such a grid is the knob's to say (_grid_range_on, read
+    per application) and then the library's: it declines before anything is touched, and the callers fall back."""
+    from . import jetblock as _blk
+    from .jets import domain, range_
+
+    if _blk._grid_native(A) is None:
+        return None
+    nrow, ncol = A.jet.s["ops"].shape
+    n = domain(A).length() // ncol
+    if any(domain(op).length() != n or range_(op).length() != n for op in A.jet.s["ops"].ravel()):
+        return None
+    return n
+
+
+def _grid_chunk_bounds(n: int, nchunks: int):
+    """Ranges of positions inside a block of n elements: bounds on 64 KiB boundaries like _chunk_bounds' where the block is that long, else
+    on 64-element (>= 256-byte) ones; the last range ends with the block."""
+    step = -(-n // nchunks)
+    grain = 16384 if step >= 16384 else 64
+    step = -(-step // grain) * grain
+    lo = 0
+    while lo < n:
+        cnt = builtins.min(step, n - lo)
+        yield lo, cnt
+        lo += cnt
+
+
+def _pipelined(xch, out, nchunks: int, kernel, finish=None, grid_n=None):
     """kernel(lo, cnt) for every element range of `out`, the exchange of a finished range (xch.send) enqueued behind its kernel, so it
     runs under the next range's kernel; then finish() -- by default xch.join(), and True.  None when the library declines
-    (JH_ERR_UNSUPPORTED) before anything was enqueued: the caller then takes its unpipelined route.  A decline after that raises."""
+    (JH_ERR_UNSUPPORTED) before anything was enqueued: the caller then takes its unpipelined route.  A decline after that raises.
+    grid_n: `out` is the domain vector of a grid of blocks of grid_n elements -- the ranges are positions inside a block and a finished
+    range's exchange is its K pieces (k * grid_n + lo, cnt)."""
     from ._ffi import JetsHipError
+
+    from . import chains as _chn
 
     xch.open(out)
     done = 0
+    bounds = _chunk_bounds(out.length(), nchunks) if grid_n is None else _grid_chunk_bounds(grid_n, nchunks)
+    pieces = (0,) if grid_n is None else [k * grid_n for k in builtins.range(out.length() // grid_n)]
     try:
-        for lo, cnt in _chunk_bounds(out.length(), nchunks):
+        for lo, cnt in bounds:
             kernel(lo, cnt)
-            xch.send(lo, cnt)
+            if grid_n is not None:
+                _chn.STATS["grid_range_calls"] += 1
+            for at in pieces:
+                xch.send(at + lo, cnt)
             done += 1
     except JetsHipError as e:
         if e.status == 4 and done == 0:
@@ -420,6 +481,12 @@ def _pipelined_routes(xch, local_op, sc) -> dict:
     from . import jetblock as _blk
 
     nchunks = int(os.environ.get("JETS_AR_CHUNKS", "4"))
+    local_n = _grid_block_len(local_op)
+
+    def grid_n_of(A):
+        """The block length to cut over when `A` is a grid and the knob is on (read per application), else None: the flat domain."""
+        n = local_n if A is local_op else _grid_block_len(A)
+        return n if n is not None and _grid_range_on() else None
 
     def native_of(A):
         if nchunks <= 1 or not xch.ready() or not _blk.isblockop(A):
@@ -440,14 +507,16 @@ def _pipelined_routes(xch, local_op, sc) -> dict:
         nat = native_of(A)
         if nat is None:
             return A is local_op and sc.has_adj and weighted(m, d, sc.adjoint())
-        return _pipelined(xch, m, nchunks, lambda lo, cnt: check(lib.jh_blockop_mul_adj_range(nat.handle, m.handle, d.handle, lo, cnt)))
+        return _pipelined(xch, m, nchunks, lambda lo, cnt: check(lib.jh_blockop_mul_adj_range(nat.handle, m.handle, d.handle, lo, cnt)),
+                          grid_n=grid_n_of(A))
 
     def pipelined_normal(y, A, m):
         """The fused A'A in `nchunks` element ranges (jh_blockop_normal_mul_range), exchanged like the adjoint's."""
         nat = native_of(A)
         if nat is None:
             return A is local_op and sc.has_normal and weighted(y, m, sc.normal())
-        return _pipelined(xch, y, nchunks, lambda lo, cnt: check(lib.jh_blockop_normal_mul_range(nat.handle, y.handle, m.handle, lo, cnt)))
+        return _pipelined(xch, y, nchunks, lambda lo, cnt: check(lib.jh_blockop_normal_mul_range(nat.handle, y.handle, m.handle, lo, cnt)),
+                          grid_n=grid_n_of(A))
 
     def pipelined_step(u, v, w, alpha, beta):
         """jh_blockop_bidiag_step in `nchunks` element ranges, enqueued back to back: every range adds its share of ||u||^2 to a device-side
@@ -466,7 +535,7 @@ def _pipelined_routes(xch, local_op, sc) -> dict:
             return r
         check(lib.jh_normsq_reset())
         return _pipelined(xch, w, nchunks, lambda lo, cnt: check(lib.jh_blockop_bidiag_step_range(
-            nat.handle, u.handle, v.handle, w.handle, float(alpha), float(beta), lo, cnt, None)), finish=xch.normsq)
+            nat.handle, u.handle, v.handle, w.handle, float(alpha), float(beta), lo, cnt, None)), finish=xch.normsq, grid_n=grid_n_of(local_op))
 
     return dict(pipelined_adj=pipelined_adj, pipelined_step=pipelined_step, pipelined_normal=pipelined_normal)
 
@@ -603,6 +672,19 @@ class TeamOp:
         # members whose local operators are WEIGHTED chains (W_k o A_k, ...: _ShardChains): the one-pass step and the normal operator range by
         # range through each member's own chain handles, which live in that member's context (built on first use there, released by close())
         self._chains = [None if nat is not None else _ShardChains(A) for nat, A in zip(self._natives, self.local_ops)]
+        # members that are N x (2 .. 4) grids of equal blocks of ONE length: the ranges are cut over it when the knob grid_range is 1 (_team_grid_n)
+        lens = {_grid_block_len(A) for A in self.local_ops}
+        self._grid_n = lens.pop() if len(lens) == 1 else None
+
+    def _team_grid_n(self):
+        """The block length to cut the ranges over, or None (the flat domain).  Knobs are per context: grid_range is read in EVERY member's
+        context, and members that disagree are an error here, before any member's kernel has touched its u."""
+        if self._grid_n is None:
+            return None
+        on = [_grid_range_on() for _ in self.team.each()]
+        if any(on) and not all(on):
+            raise ValueError(f"knob grid_range differs between the team's contexts ({[int(v) for v in on]}): set it in every member's context")
+        return self._grid_n if on[0] else None
 
     @property
     def chain_step(self) -> bool:
@@ -674,12 +756,22 @@ class TeamOp:
 
         if native and any(n is None for n in self._natives):
             return False
-        for lo, cnt in _chunk_bounds(m[0].length(), self.nchunks):
+        from . import chains as _chn
+
+        # members that are N x (2 .. 4) grids (knob grid_range = 1): ranges of positions inside a block, a finished range's K pieces exchanged
+        # (a group per piece: a group holds one collective per member)
+        grid_n = self._team_grid_n() if native else None
+        bounds = _chunk_bounds(m[0].length(), self.nchunks) if grid_n is None else _grid_chunk_bounds(grid_n, self.nchunks)
+        pieces = (0,) if grid_n is None else [k * grid_n for k in builtins.range(m[0].length() // grid_n)]
+        for lo, cnt in bounds:
             for k, _ in self.team.each():
                 enqueue_range(k, lo, cnt)
-            with self.team.group():
-                for k in builtins.range(self.team.world):
-                    check(lib.jh_comm_allreduce_sum_range(m[k].handle, lo, cnt))
+                if grid_n is not None:
+                    _chn.STATS["grid_range_calls"] += 1
+            for at in pieces:
+                with self.team.group():
+                    for k in builtins.range(self.team.world):
+                        check(lib.jh_comm_allreduce_sum_range(m[k].handle, at + lo, cnt))
         for _ in self.team.each():
             check(lib.jh_comm_join())
         return True
