@@ -401,7 +401,21 @@ int jh_blocksum_mul_adj_typed(int nterms, const jh_blockop *const *ops, const do
  * jh_lsqr_solve_chain / jh_cgls_solve_chain iterate on it, host-driven (the warm start is one step into a scratch domain vector; CGLS's first pass
  * is the derived NORMAL grid chain).  The checks of jh_chain_bidiag_step hold unchanged, all before anything is touched.  Counter
  * "last_grid_chain_step_shape": bit 0 nontemporal loads, bit 1 rows in parts.  jh_chain_apply_range and jh_chain_bidiag_step_range decline grid
- * chains under either setting.
+ * chains under either setting -- unless knob "grid_chain_range" = 1:
+ * GRID CHAIN RANGE (knob "grid_chain_range" = 1; the default is 0, with which both calls decline a grid chain as before, before anything is
+ * touched): jh_chain_apply_range takes an ADJOINT or NORMAL grid chain, and jh_chain_bidiag_step_range a FORWARD grid chain when "grid_chain_step"
+ * is 1 as well (a whole-vector knob also governs the ranged form, as for GRID RANGE).  A grid kernel's lane owns one pack position of the blocks
+ * across all K columns, so first_elem and count are positions INSIDE a block of n elements, not a piece of the flat K n domain vector:
+ * 0 <= first_elem, first_elem + count <= n, first_elem * s and count * s multiples of 16 bytes except that the last range may end with the block;
+ * count == 0 is a no-op; anything else JH_ERR_INVALID.  One call reads those positions of every row of the range vector (ADJOINT; the step: of
+ * every u_i, which it updates) or of the K pieces of x (NORMAL; the step: of v) and writes the K pieces out_k[first_elem, first_elem + count)
+ * and nothing else -- a host exchanges a finished range as K calls of jh_comm_allreduce_sum_range at k n + first_elem.  `accumulate` as in
+ * jh_chain_apply; the step returns the range's share of ||u||^2 or (normsq NULL) adds it to the context's accumulator in enqueue order.  The
+ * checks of the whole-vector calls hold, all before anything is touched.  u always has the bits of the whole-vector call; out / w have them
+ * wherever both walk the rows in one part (always with "adj_split" = 0), tolerance parity where the many-small-rows split walk (chosen from the
+ * RANGE's pack count) cuts the rows differently.  Nontemporal loads are chosen from the WHOLE vector's bytes.  Counter
+ * "last_grid_chain_range_shape": bit 0 nontemporal loads, bit 1 rows in parts.  FORWARD chains stay declined by jh_chain_apply_range (no
+ * exchange); jh_*_solve_partitioned / _team, the graph-replayed loops, K > 4 and complex scalar stages decline under either setting.
  * JH_ERR_UNSUPPORTED (take the stage-by-stage chain): operators that are not tall or such a grid / elementwise / equal rows, one-row operators,
  * dense or nonlinear grid children, K > 4, arrays not aligned like their scalar. */
 typedef struct jh_chain jh_chain;
@@ -427,7 +441,11 @@ int jh_chain_apply(const jh_chain *chain, jh_bvec *out, const jh_bvec *x, int ac
  * parts than the whole-vector call, tolerance parity; with jh_tune_set("adj_split", 0), or wherever both walk the rows in one part, the bits are
  * jh_chain_apply's.  Counter "last_adj_parts" is the call's.  JH_ERR_INVALID: bounds outside the vector or off the 16-byte grid.
  * JH_ERR_UNSUPPORTED: a FORWARD chain (it needs no exchange), or the operator was pointed again since the chain's row table was built and
- * the library stream is capturing (the table's copy to the device would be captured; apply once outside the capture). */
+ * the library stream is capturing (the table's copy to the device would be captured; apply once outside the capture).
+ * A chain through an N x (2 .. 4) grid: JH_ERR_UNSUPPORTED unless the knob "grid_chain_range" is 1 (the default is 0).  With 1 the RANGE MEANS
+ * POSITIONS INSIDE A BLOCK of n elements -- 0 <= first_elem, first_elem + count <= n, on 16-byte boundaries except that the last range may end
+ * with the block -- and the K pieces out_k[first_elem, first_elem + count) are written, from those positions of every row of x (ADJOINT) or of
+ * the K pieces of x (NORMAL): jh_chain_create, GRID CHAIN RANGE. */
 int jh_chain_apply_range(const jh_chain *chain, jh_bvec *out, const jh_bvec *x, int accumulate, int64_t first_elem, int64_t count);
 int jh_chain_destroy(jh_chain *chain);
 /* One Golub-Kahan / LSQR step over a FORWARD chain L = R o A o P (weighted least squares: lsqr(W o A o M, b), docs/src/index.md:235-246;
@@ -459,7 +477,11 @@ int jh_chain_bidiag_step(const jh_chain *fwd, jh_bvec *u, const jh_bvec *v, jh_b
  * ranged ADJOINT chain.  Counter "last_adj_parts" is the call's.  JH_ERR_INVALID: not a FORWARD chain, vectors of the wrong length or aliased,
  * bounds outside the vector or off the 16-byte grid.  JH_ERR_UNSUPPORTED before anything is touched: R and R^H together exceed 4 range-side
  * stages, a vector not aligned like its scalar, a grid chain, or the operator was pointed again since the row table was built while the library
- * stream is capturing. */
+ * stream is capturing.
+ * A FORWARD chain through an N x (2 .. 4) grid is taken when the knobs "grid_chain_range" AND "grid_chain_step" are both 1 (the defaults are 0).
+ * Then the RANGE MEANS POSITIONS INSIDE A BLOCK of n elements -- 0 <= first_elem, first_elem + count <= n, on 16-byte boundaries except that the
+ * last range may end with the block: those positions of every u_i are updated, the K pieces w_k[first_elem, first_elem + count) written, and the
+ * range's share of ||u||^2 returned or deferred as above (jh_chain_create, GRID CHAIN RANGE). */
 int jh_chain_bidiag_step_range(const jh_chain *fwd, jh_bvec *u, const jh_bvec *v, jh_bvec *w, double alpha, double beta, int64_t first_elem, int64_t count,
                                double *normsq);
 
@@ -660,7 +682,7 @@ int jh_team_normal_mul(int n, const jh_blockop *const *ops, jh_bvec *const *ys, 
  * aligned loads of diagonals laid out like the range vector: -1 rows of 64 KiB or more, 0 never, 1 always; same bits), "tall_f" (F(m) of a tall nonlinear operator of elementwise children -- jh_blockop_f -- on the tall tiling: 1 yes, 0 the
  * general kernels; same bits), "dense_list_shared" (round 6: the rows pass of y = B x for DENSE children whose columns are off the 16-byte grid numbers its
  * chunks XCD by XCD and loads temporally, so the 128-byte line two neighbouring rows share is fetched from HBM once: 1 yes, 0 round 5's pass; same bits),
- * "dense_list_rl_min" (log2 of the fewest row lanes per workgroup of that pass, 0: automatic), "red_blocks_wave" (round 6: jh_norm_blocks / jh_dot_blocks of many blocks of at most 16 KiB with a wave per block in one launch: 1 yes, 0 a workgroup per block + the fold; within the reductions' tolerance of each other), "adj_bare_chain" (round 6: jh_blockop_mul_adj and jh_blockop_normal_mul of a tall operator with rows of several kinds, or rows off the 16-byte grid, of up to 4 MiB on the chain kernels with empty stage lists -- packed row records --: 1 yes, 0 the MIXED tall kernel; same bits unless the split walk's part count changes), "adj_thin_mixed" (round 6: the adjoint of a tall operator with rows of several kinds on thin workgroups when fat ones would leave CUs idle -- rows of 1-8 MiB --: 1 yes, 0 round 5's shapes; same bits unless the split walk's part count changes), "grid_normal" (round 6: jh_blockop_normal_mul on N x (2 .. 4) grids of equal elementwise blocks -- diagonals, zero / identity / scalar blocks -- in one pass: 1 yes, 2 grids of plain diagonals only, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_step" (jh_blockop_bidiag_step, jh_lsqr_solve and jh_cgls_solve on N x (2 .. 4) grids of equal elementwise blocks in one pass per step: 1 yes, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_chain_step" (jh_chain_bidiag_step, jh_lsqr_solve_chain and jh_cgls_solve_chain on a FORWARD chain through an N x (2 .. 4) grid in one pass per step: 1 yes, 0 -- the default -- JH_ERR_UNSUPPORTED as before; same bits: see jh_chain_create, GRID CHAIN STEP), "grid_range" (jh_blockop_mul_adj_range, jh_blockop_normal_mul_range and jh_blockop_bidiag_step_range on N x (2 .. 4) grids of equal elementwise blocks, the range being positions inside a block: 1 yes, 0 -- the default -- JH_ERR_UNSUPPORTED as before; see jh_blockop_mul_adj_range, GRID RANGE), "grid_chain" (jh_chain_create on N x (2 .. 4) grids of equal elementwise blocks -- fused chains A' o W o A, (W o A)', W o A through a multi-parameter operator: 1 yes, 0 JH_ERR_UNSUPPORTED as before, the caller runs the composite stage by stage; same bits), "dense_combine" (round 6: operators whose non-zero blocks are
+ * "dense_list_rl_min" (log2 of the fewest row lanes per workgroup of that pass, 0: automatic), "red_blocks_wave" (round 6: jh_norm_blocks / jh_dot_blocks of many blocks of at most 16 KiB with a wave per block in one launch: 1 yes, 0 a workgroup per block + the fold; within the reductions' tolerance of each other), "adj_bare_chain" (round 6: jh_blockop_mul_adj and jh_blockop_normal_mul of a tall operator with rows of several kinds, or rows off the 16-byte grid, of up to 4 MiB on the chain kernels with empty stage lists -- packed row records --: 1 yes, 0 the MIXED tall kernel; same bits unless the split walk's part count changes), "adj_thin_mixed" (round 6: the adjoint of a tall operator with rows of several kinds on thin workgroups when fat ones would leave CUs idle -- rows of 1-8 MiB --: 1 yes, 0 round 5's shapes; same bits unless the split walk's part count changes), "grid_normal" (round 6: jh_blockop_normal_mul on N x (2 .. 4) grids of equal elementwise blocks -- diagonals, zero / identity / scalar blocks -- in one pass: 1 yes, 2 grids of plain diagonals only, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_step" (jh_blockop_bidiag_step, jh_lsqr_solve and jh_cgls_solve on N x (2 .. 4) grids of equal elementwise blocks in one pass per step: 1 yes, 0 JH_ERR_UNSUPPORTED as before; same bits), "grid_chain_step" (jh_chain_bidiag_step, jh_lsqr_solve_chain and jh_cgls_solve_chain on a FORWARD chain through an N x (2 .. 4) grid in one pass per step: 1 yes, 0 -- the default -- JH_ERR_UNSUPPORTED as before; same bits: see jh_chain_create, GRID CHAIN STEP), "grid_range" (jh_blockop_mul_adj_range, jh_blockop_normal_mul_range and jh_blockop_bidiag_step_range on N x (2 .. 4) grids of equal elementwise blocks, the range being positions inside a block: 1 yes, 0 -- the default -- JH_ERR_UNSUPPORTED as before; see jh_blockop_mul_adj_range, GRID RANGE), "grid_chain_range" (jh_chain_apply_range on an ADJOINT / NORMAL chain and -- with "grid_chain_step" = 1 as well -- jh_chain_bidiag_step_range on a FORWARD chain through an N x (2 .. 4) grid, the range being positions inside a block: 1 yes, 0 -- the default -- JH_ERR_UNSUPPORTED as before; see jh_chain_create, GRID CHAIN RANGE; read-only "last_grid_chain_range_shape": bit 0 nontemporal loads, bit 1 rows in parts), "grid_chain" (jh_chain_create on N x (2 .. 4) grids of equal elementwise blocks -- fused chains A' o W o A, (W o A)', W o A through a multi-parameter operator: 1 yes, 0 JH_ERR_UNSUPPORTED as before, the caller runs the composite stage by stage; same bits), "dense_combine" (round 6: operators whose non-zero blocks are
  * all DENSE children sum the products of a block line from CSR lists in one launch: 1 yes, 0 the general step lists; same bits);
  * round 4: "cg_dev" (jh_cgls_solve / jh_cgnr_solve with the recurrences on the device, graph-replayed unless lsqr_graph = 0: 1 automatic -- CGLS
  * like lsqr_graph, CG through the fused A'A up to 2 GiB of coefficients --, 2 at any size, 0 never: the host loops; within solver tolerance

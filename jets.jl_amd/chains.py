@@ -37,7 +37,7 @@ STATS = {"chain_calls": 0, "sum_terms_fused": 0, "bcast_calls": 0,    # how ofte
          "chain_step_range_calls": 0,                                 # one-pass steps on an element range (jh_chain_bidiag_step_range: weighted shards and teams; also in chain_range_calls)
          "grid_chain_calls": 0,                                       # fused runs through an N x (2 .. 4) grid (also counted in chain_calls / chain_solve_calls)
          "grid_step_calls": 0, "grid_solve_calls": 0,                 # the solvers on a bare grid: one-pass steps (jh_blockop_bidiag_step), native LSQR / CGLS solves
-         "grid_range_calls": 0}                                       # ranged calls on a bare grid (jh_blockop_{mul_adj,normal_mul,bidiag_step}_range with the knob grid_range = 1: sharded grids and teams)
+         "grid_range_calls": 0}                                       # ranged calls on a grid (sharded grids and teams): a bare one (jh_blockop_{mul_adj,normal_mul,bidiag_step}_range, knob grid_range = 1) or a chain through one (jh_chain_apply_range / jh_chain_bidiag_step_range, knob grid_chain_range = 1)
 
 
 # ------------------------------------------------------------------------------ classification -----
@@ -181,6 +181,8 @@ class ChainHandle:
         self.grid = tall.kind == "grid"
         nrow = tall.base.jet.s["ops"].shape[0]
         ndom = domain(tall.base).length()                 # (a grid's domain is its K blocks: K n elements)
+        # a grid chain's ranged calls (knob grid_chain_range) take positions inside a block of this many elements, not a piece of the K n domain
+        self.block_len = ndom // tall.base.jet.s["ops"].shape[1] if self.grid else None
         nblk = range_(tall.base).length() // nrow         # one block row of the range
         es = np.dtype(domain(tall.base).eltype()).itemsize
 
@@ -226,20 +228,26 @@ class ChainHandle:
         return out
 
     def apply_range(self, out, x, first: int, count: int, accumulate: int = 0):
-        """The ADJOINT / NORMAL chain on the domain's elements [first, first + count) (jh_chain_apply_range): out's other elements stay as they are."""
+        """The ADJOINT / NORMAL chain on the domain's elements [first, first + count) (jh_chain_apply_range): out's other elements stay as they are.
+        Through a grid (knob grid_chain_range = 1): positions [first, first + count) inside a block (block_len), the K pieces of out."""
         check(lib.jh_chain_apply_range(self._h, out.handle, x.handle, accumulate, int(first), int(count)))
         STATS["chain_range_calls"] += 1
+        if self.grid:
+            STATS["grid_chain_calls"] += 1
         return out
 
     def bidiag_step_range(self, u, v, w, alpha: float, beta: float, first: int, count: int, read_normsq: bool = False):
         """The Golub-Kahan step of a FORWARD chain on the domain's elements [first, first + count) (jh_chain_bidiag_step_range): those columns of
         every row of u, that range of w.  read_normsq: returns the range's share of ||u||^2 (synchronises); otherwise the share joins the
-        context's deferred accumulator (jh_normsq_reset / jh_normsq_read) and None is returned."""
+        context's deferred accumulator (jh_normsq_reset / jh_normsq_read) and None is returned.  Through a grid (knobs grid_chain_range and
+        grid_chain_step = 1): positions [first, first + count) inside a block (block_len) of every u_i, the K pieces of w."""
         out = C.c_double(0) if read_normsq else None
         check(lib.jh_chain_bidiag_step_range(self._h, u.handle, v.handle, w.handle, float(alpha), float(beta), int(first), int(count),
                                              C.byref(out) if read_normsq else None))
         STATS["chain_range_calls"] += 1
         STATS["chain_step_range_calls"] += 1
+        if self.grid:
+            STATS["grid_chain_calls"] += 1
         return out.value if read_normsq else None
 
     def close(self):
@@ -479,7 +487,8 @@ def stages_of(op: Jop):
 
 def one_run(stages: Sequence, cache: ChainCache, tag, ctype: int, make: bool = True, grid: bool = True):
     """When the WHOLE stage list is one fused run of chain type `ctype`: its ChainHandle (make=True; None when the library declines) or True
-    (make=False: planned, no handle built).  None otherwise.  grid=False: not a run through a grid (the row partition has no grid chains)."""
+    (make=False: planned, no handle built).  None otherwise.  grid=False: not a run through a grid (the row partition plans grid chains only
+    with the knob grid_chain_range = 1: rowpart._ShardChains)."""
     if not ENABLED[0]:
         return None
     steps = plan(stages, cache, tag)
@@ -491,6 +500,16 @@ def one_run(stages: Sequence, cache: ChainCache, tag, ctype: int, make: bool = T
         return True
     _, ctype, tall, pre, mid, post, _members = steps[0]
     return _chain_handle(cache, ctype, tall, pre, mid, post)
+
+
+def run_anchor(stages: Sequence, cache: ChainCache, tag, ctype: int):
+    """The anchor Stage (kind 'tall' or 'grid') of a stage list that is ONE fused run of chain type `ctype`, else None."""
+    if not ENABLED[0]:
+        return None
+    steps = plan(stages, cache, tag)
+    if len(steps) != 1 or steps[0][0] != "chain" or steps[0][1] != ctype:
+        return None
+    return steps[0][2]
 
 
 def has_chain(steps) -> bool:

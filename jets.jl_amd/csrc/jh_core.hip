@@ -994,6 +994,7 @@ int jh_tune_set(const char *name, int64_t value)
     else if (!strcmp(name, "grid_step")) { JH_REQUIRE(value == 0 || value == 1, "grid_step must be 0 or 1"); c.grid_step = value; }
     else if (!strcmp(name, "grid_chain_step")) { JH_REQUIRE(value == 0 || value == 1, "grid_chain_step must be 0 or 1"); c.grid_chain_step = value; }
     else if (!strcmp(name, "grid_range")) { JH_REQUIRE(value == 0 || value == 1, "grid_range must be 0 or 1"); c.grid_range = value; }
+    else if (!strcmp(name, "grid_chain_range")) { JH_REQUIRE(value == 0 || value == 1, "grid_chain_range must be 0 or 1"); c.grid_chain_range = value; }
     else if (!strcmp(name, "fwd_anchor")) { JH_REQUIRE(value >= -1 && value <= 1, "fwd_anchor must be -1 (rows of >= 64 KiB that are not whole packs), 0 (never) or 1 (always)"); c.fwd_anchor = value; }
     else if (!strcmp(name, "ua_nt")) { JH_REQUIRE(value >= -1 && value <= 1, "ua_nt must be -1 (temporal accesses on rows off the 16-byte grid), 0 (temporal always) or 1 (nontemporal always)"); c.ua_nt = value; }
     else if (!strcmp(name, "tall_unaligned")) { JH_REQUIRE(value >= 0 && value <= 1, "tall_unaligned must be 0 (general kernels) or 1 (under-aligned tall kernels)"); c.tall_unaligned = value; }
@@ -1084,6 +1085,8 @@ int jh_tune_get(const char *name, int64_t *value)
     else if (!strcmp(name, "last_grid_chain_step_shape")) *value = c.last_grid_chain_step_shape;
     else if (!strcmp(name, "grid_range")) *value = c.grid_range;
     else if (!strcmp(name, "last_grid_range_shape")) *value = c.last_grid_range_shape;
+    else if (!strcmp(name, "grid_chain_range")) *value = c.grid_chain_range;
+    else if (!strcmp(name, "last_grid_chain_range_shape")) *value = c.last_grid_chain_range_shape;
     else if (!strcmp(name, "fwd_anchor")) *value = c.fwd_anchor;
     else if (!strcmp(name, "ua_nt")) *value = c.ua_nt;
     else if (!strcmp(name, "tall_f")) *value = c.tall_f;

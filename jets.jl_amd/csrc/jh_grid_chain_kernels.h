@@ -32,16 +32,19 @@ namespace {
 // MODE 0 FORWARD, 1 ADJOINT, 2 NORMAL.  Launched on (tiles, parts): workgroup row blockIdx.y walks block rows [y, y + 1) * rows_per_part.  FORWARD: the
 // parts are independent row groups (no fold); ADJOINT / NORMAL: part_out != NULL -- the split walk, slab y of part_out (K n scalars apart) gets the
 // part's row sums and the fold (k_fold_parts) and the list after A' (k_chain_finish) follow in launches of their own.
+// The lanes cover the scalars [s_begin, s_end) of a block (the whole block: 0, n_scalars; a range of it: jh_chain_apply_range with the knob
+// grid_chain_range -- a range shorter than one pack ends with the block and is loaded from s_end - NS); n_scalars stays the stride of the rows of the
+// range vector, of the K pieces of the domain vectors (the domain-side lists address coef + k n_scalars + sk) and of the slabs.
 template <typename S, int E, int NS, int K, int DEPTH, bool NT, int MODE, int NW>
 __global__ __launch_bounds__(256) void k_grid_chain(const jh_dev_block *__restrict__ blocks, int64_t nrow, const ChainArgs ca, S *__restrict__ out,
                                                     const S *__restrict__ in, int64_t n_scalars, int accumulate, int64_t rows_per_part,
-                                                    S *__restrict__ part_out, const ChainProg *__restrict__ mid_dev)
+                                                    S *__restrict__ part_out, const ChainProg *__restrict__ mid_dev, int64_t s_begin, int64_t s_end)
 {
     typedef typename vec_of<S, NS>::type V;
     constexpr int NWA = NW > 0 ? NW : 1, RW = K + NW;
-    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;
-    const bool ok = s0 < n_scalars;
-    const int64_t sk = pack_start<NS>(ok ? s0 : 0, n_scalars);
+    const int64_t s0 = s_begin + ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;
+    const bool ok = s0 < s_end;
+    const int64_t sk = pack_start<NS>(ok ? s0 : s_begin, s_end);
     const bool rmw = accumulate == 1 || accumulate == -1;
     const bool has_mid = NW > 0 || (ca.mid.st[0] & 15u) != CK_NONE;
     V x[K], acc[K];
@@ -166,14 +169,20 @@ __global__ __launch_bounds__(256) void k_grid_chain(const jh_dev_block *__restri
 // rows in flight: two for every K (K x 2 coefficient packs per lane, and the weights'); K = 2 at four rows spilled SGPRs with two range weights
 template <int K> struct grid_chain_depth { static constexpr int value = 2; };
 
+// end_elem < 0: the whole block; else the positions [first_elem, end_elem) of every block (jh_chain_apply_range, MODE != 0; the caller has checked the
+// bounds): the same kernel over those lanes.  The parts are chosen from the RANGE's pack count, the slabs keep the block's stride (parts x K x n_scalars,
+// of which a range touches its share), the fold and the list after A' run over each of the K pieces' range, and the nontemporal rule sees the WHOLE
+// vector's bytes, so that a range streams like the whole vector.
 template <typename S, int E, int NS, int K, int MODE>
-int launch_grid_chain_k(const jh_chain *ch, int prog, void *out, const void *in, int64_t n_scalars, int accumulate)
+int launch_grid_chain_k(const jh_chain *ch, int prog, void *out, const void *in, int64_t n_scalars, int accumulate, int64_t first_elem, int64_t end_elem)
 {
     const ChainArgs &ca = prog == GRID_PROG_ADJ ? ch->adj_args : (prog == GRID_PROG_NRM ? ch->nrm_args : ch->args);
     constexpr int DEPTH = grid_chain_depth<K>::value;
     jh_context &c = jh_ctx();
     const jh_blockop *op = ch->op;
-    const int64_t packs = (n_scalars + NS - 1) / NS, gx = (packs + 255) / 256, ndom = (int64_t)K * n_scalars;
+    const bool ranged = end_elem >= 0;
+    const int64_t s_begin = ranged ? first_elem * E : 0, s_end = ranged ? end_elem * E : n_scalars;
+    const int64_t packs = (s_end - s_begin + NS - 1) / NS, gx = (packs + 255) / 256, ndom = (int64_t)K * n_scalars;
     int64_t parts = 1, rows_per_part = op->nrow;
     if (MODE == 0) {
         // FORWARD: the rows are independent; row groups of their own workgroups where one walk per tile would leave the chip short of
@@ -184,6 +193,7 @@ int launch_grid_chain_k(const jh_chain *ch, int prog, void *out, const void *in,
         // the part-count rules of the tall chains and k_grid_normal (jh_tall.hip: pick_adj_parts; adj_split = 0 keeps the ordered, bit-exact walk)
         parts = jhb::pick_adj_parts(gx, op->nrow);
         if (parts == 1 && c.adj_split < 0 && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
+        if (s_end - s_begin < NS) parts = 1;                                             // (a range shorter than one pack loads from before s_begin: one part)
     }
     if (parts > op->nrow) parts = op->nrow;
     if (parts < 1) parts = 1;
@@ -204,10 +214,11 @@ int launch_grid_chain_k(const jh_chain *ch, int prog, void *out, const void *in,
     const ChainProg *mid_dev = ch->dev_mid + prog;                                      // (ca.mid's device copy: the kernel reads it per row)
     const double streamed = ch->stream_bytes + (MODE != 2 ? (double)op->nrow * (double)n_scalars * sizeof(S) : 0.0);
     const bool nt = jh_stream_nt(streamed);
-    c.last_grid_chain_shape = (nt ? 1 : 0) | (parts > 1 ? 2 : 0) | (finish && parts > 1 ? 4 : 0);
+    if (ranged) c.last_grid_chain_range_shape = (nt ? 1 : 0) | (parts > 1 ? 2 : 0);
+    else c.last_grid_chain_shape = (nt ? 1 : 0) | (parts > 1 ? 2 : 0) | (finish && parts > 1 ? 4 : 0);
 #define JH_GRID_CHAIN(NTV, NWV)                                                                                                              \
     hipLaunchKernelGGL((k_grid_chain<S, E, NS, K, DEPTH, NTV, MODE, NWV>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, op->dev_blocks, \
-                       op->nrow, ca, (S *)out, (const S *)in, n_scalars, accumulate, rows_per_part, slabs, mid_dev)
+                       op->nrow, ca, (S *)out, (const S *)in, n_scalars, accumulate, rows_per_part, slabs, mid_dev, s_begin, s_end)
     switch (ch->nw) {
     case 0: if (nt) JH_GRID_CHAIN(true, 0); else JH_GRID_CHAIN(false, 0); break;
     case 1: if (nt) JH_GRID_CHAIN(true, 1); else JH_GRID_CHAIN(false, 1); break;
@@ -215,25 +226,32 @@ int launch_grid_chain_k(const jh_chain *ch, int prog, void *out, const void *in,
     }
 #undef JH_GRID_CHAIN
     JH_CHECK_HIP(hipGetLastError());
-    if (slabs) {
+    if (slabs && !ranged) {
         JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, ndom, parts, folded, 0, ndom));
         if (finish) {
             JH_TRY(jhb::chain_finish(ch, ca, out, folded, 0, ndom, accumulate));
         }
     }
+    if (slabs && ranged)                                                                 // (the slabs keep the whole block's stride: the range of each piece)
+        for (int k = 0; k < K; k++) {
+            const int64_t lo = (int64_t)k * n_scalars + s_begin, hi = (int64_t)k * n_scalars + s_end;
+            JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs + lo, ndom, parts, folded, lo, hi));
+            if (finish) JH_TRY(jhb::chain_finish(ch, ca, out, folded, lo, hi, accumulate));
+        }
     return JH_OK;
 }
 
+// first_elem, end_elem: positions inside a block (end_elem < 0: the whole block)
 template <int MODE>
-int launch_grid_chain(const jh_chain *ch, int prog, void *out, const void *in, int accumulate)
+int launch_grid_chain(const jh_chain *ch, int prog, void *out, const void *in, int accumulate, int64_t first_elem = 0, int64_t end_elem = -1)
 {
     const jh_blockop *op = ch->op;
     const int64_t n = op->row_len[0];
 #define JH_GRID_K(S, E, NS)                                                                                                                  \
     switch (op->ncol) {                                                                                                                    \
-    case 2: return launch_grid_chain_k<S, E, NS, 2, MODE>(ch, prog, out, in, n * E, accumulate);                                              \
-    case 3: return launch_grid_chain_k<S, E, NS, 3, MODE>(ch, prog, out, in, n * E, accumulate);                                              \
-    default: return launch_grid_chain_k<S, E, NS, 4, MODE>(ch, prog, out, in, n * E, accumulate);                                             \
+    case 2: return launch_grid_chain_k<S, E, NS, 2, MODE>(ch, prog, out, in, n * E, accumulate, first_elem, end_elem);                                              \
+    case 3: return launch_grid_chain_k<S, E, NS, 3, MODE>(ch, prog, out, in, n * E, accumulate, first_elem, end_elem);                                              \
+    default: return launch_grid_chain_k<S, E, NS, 4, MODE>(ch, prog, out, in, n * E, accumulate, first_elem, end_elem);                                             \
     }
     switch (op->dtype) {
     case JH_F32: JH_GRID_K(float, 1, 4)

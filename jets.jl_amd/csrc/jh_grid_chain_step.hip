@@ -19,17 +19,19 @@
 namespace {
 
 // OLD: beta != 0 -- u is read; else it is write-only.  (Decided at compile time: jh_grid_step.hip's lesson -- the choice per row spilled SGPRs.)
+// The lanes cover the scalars [s_begin, s_end) of a block (the whole block: 0, n_scalars; a range of it: jh_chain_bidiag_step_range with the knob
+// grid_chain_range); n_scalars stays the stride of the rows of u, of the pieces of v and w (and of the domain-side lists' coefficients) and of the slabs.
 template <typename S, int E, int NS, int K, int DEPTH, bool NT, int NW, bool OLD>
 __global__ __launch_bounds__(256) void k_grid_chain_step(const jh_dev_block *__restrict__ blocks, int64_t nrow, const ChainArgs ca, S *__restrict__ w,
                                                          const S *__restrict__ v, S *__restrict__ u, int64_t n_scalars, S alpha, S beta,
                                                          double *__restrict__ partials, int64_t rows_per_part, S *__restrict__ part_out,
-                                                         const ChainProg *__restrict__ mid_dev)
+                                                         const ChainProg *__restrict__ mid_dev, int64_t s_begin, int64_t s_end)
 {
     typedef typename vec_of<S, NS>::type V;
     constexpr int NWA = NW > 0 ? NW : 1, RW = K + NW;
-    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;
-    const bool ok = s0 < n_scalars;
-    const int64_t sk = pack_start<NS>(ok ? s0 : 0, n_scalars);
+    const int64_t s0 = s_begin + ((int64_t)blockIdx.x * 256 + threadIdx.x) * NS;
+    const bool ok = s0 < s_end;
+    const int64_t sk = pack_start<NS>(ok ? s0 : s_begin, s_end);                          // (a range shorter than one pack ends with the block: loaded from s_end - NS)
     const int e0 = ok ? (int)(s0 - sk) : 0;                                               // a row's partial last pack counts the scalars it OWNS
     const bool has_mid = NW > 0 || (ca.mid.st[0] & 15u) != CK_NONE;
     V x[K], acc[K];
@@ -151,16 +153,23 @@ template <typename S, int K, int NW, bool OLD> struct grid_chain_step_depth {
     static constexpr int value = (sizeof(S) == 4 && NW == 2 && K + (OLD ? 1 : 0) >= 4) ? 1 : 2;
 };
 
+// end_elem < 0: the whole block; else the positions [first_elem, end_elem) of every block (jh_chain_bidiag_step_range, knob grid_chain_range): the same
+// kernel over those lanes, the parts chosen from the RANGE's pack count, the slabs at the block's stride, the fold and Q over each of the K pieces'
+// range, ||u||^2 deferred (normsq == NULL: added to the context's accumulator in enqueue order)
 template <typename S, int E, int NS, int K>
-int launch_grid_chain_step_k(const jh_chain *ch, void *u, const void *v, void *w, int64_t n_scalars, double alpha, double beta, double *normsq)
+int launch_grid_chain_step_k(const jh_chain *ch, void *u, const void *v, void *w, int64_t n_scalars, double alpha, double beta, double *normsq,
+                             int64_t first_elem, int64_t end_elem)
 {
     const ChainArgs &ca = ch->step_args;
     jh_context &c = jh_ctx();
     const jh_blockop *op = ch->op;
-    const int64_t packs = (n_scalars + NS - 1) / NS, gx = (packs + 255) / 256, ndom = (int64_t)K * n_scalars;
+    const bool ranged = end_elem >= 0;
+    const int64_t s_begin = ranged ? first_elem * E : 0, s_end = ranged ? end_elem * E : n_scalars;
+    const int64_t packs = (s_end - s_begin + NS - 1) / NS, gx = (packs + 255) / 256, ndom = (int64_t)K * n_scalars;
     // the part-count rules of the grid chains' ADJOINT / NORMAL walks (launch_grid_chain_k; adj_split = 0 keeps the ordered, bit-exact walk)
     int64_t parts = jhb::pick_adj_parts(gx, op->nrow), rows_per_part = op->nrow;
     if (parts == 1 && c.adj_split < 0 && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
+    if (s_end - s_begin < NS) parts = 1;                                                 // (a range shorter than one pack loads from before s_begin: one part)
     if (parts > op->nrow) parts = op->nrow;
     if (parts < 1) parts = 1;
     if (parts > 1) {
@@ -180,12 +189,12 @@ int launch_grid_chain_step_k(const jh_chain *ch, void *u, const void *v, void *w
     // streamed per pass: the coefficients and the weights, and u -- written, and read as well when beta != 0
     const bool nt = jh_stream_nt(ch->stream_bytes + (beta != 0.0 ? 2.0 : 1.0) * (double)op->nrow * (double)n_scalars * sizeof(S));
     c.last_adj_parts = parts;
-    c.last_grid_chain_step_shape = (nt ? 1 : 0) | (parts > 1 ? 2 : 0);
+    (ranged ? c.last_grid_chain_range_shape : c.last_grid_chain_step_shape) = (nt ? 1 : 0) | (parts > 1 ? 2 : 0);
     const ChainProg *mid_dev = ch->dev_mid + GRID_PROG_OWN;                              // (R: the FORWARD chain's own range-side list)
 #define JH_GCS(NTV, NWV, OLDV)                                                                                                               \
     hipLaunchKernelGGL((k_grid_chain_step<S, E, NS, K, grid_chain_step_depth<S, K, NWV, OLDV>::value, NTV, NWV, OLDV>), dim3((unsigned)gx, (unsigned)parts), \
                        dim3(256), 0, c.stream, op->dev_blocks, op->nrow, ca, (S *)w, (const S *)v, (S *)u, n_scalars, (S)alpha, (S)beta, c.part_dev,   \
-                       rows_per_part, slabs, mid_dev)
+                       rows_per_part, slabs, mid_dev, s_begin, s_end)
 #define JH_GCS_OLD(NTV, NWV)                   \
     if (beta != 0.0) JH_GCS(NTV, NWV, true);   \
     else JH_GCS(NTV, NWV, false)
@@ -201,27 +210,35 @@ int launch_grid_chain_step_k(const jh_chain *ch, void *u, const void *v, void *w
 #undef JH_GCS_OLD
 #undef JH_GCS
     JH_CHECK_HIP(hipGetLastError());
-    if (slabs) {
+    if (slabs && !ranged) {
         JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, ndom, parts, folded, 0, ndom));
         if (finish) JH_TRY(jhb::chain_finish(ch, ca, w, folded, 0, ndom, 0));
     }
-    return jhb::step_finish_normsq(gx * parts, normsq);
+    if (slabs && ranged)                                                                 // (the slabs keep the whole block's stride: the range of each piece)
+        for (int k = 0; k < K; k++) {
+            const int64_t lo = (int64_t)k * n_scalars + s_begin, hi = (int64_t)k * n_scalars + s_end;
+            JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs + lo, ndom, parts, folded, lo, hi));
+            if (finish) JH_TRY(jhb::chain_finish(ch, ca, w, folded, lo, hi, 0));
+        }
+    return jhb::step_finish_normsq(gx * parts, normsq, ranged);
 }
 
 }  // namespace
 
 namespace jhb {
 
-// the caller (jh_chain_bidiag_step) has checked the knob, the handle (a FORWARD grid chain, R + R^H within one list), the vectors and the row table
-int grid_chain_step(const jh_chain *ch, void *u, const void *v, void *w, double alpha, double beta, double *normsq)
+// the caller (jh_chain_bidiag_step / _range) has checked the knobs, the handle (a FORWARD grid chain, R + R^H within one list), the vectors, the row
+// table and (ranged) the bounds
+static int grid_chain_step_by_dtype(const jh_chain *ch, void *u, const void *v, void *w, double alpha, double beta, double *normsq, int64_t first_elem,
+                                    int64_t end_elem)
 {
     const jh_blockop *op = ch->op;
     const int64_t n = op->row_len[0];
 #define JH_GCS_K(S, E, NS)                                                                                           \
     switch (op->ncol) {                                                                                             \
-    case 2: return launch_grid_chain_step_k<S, E, NS, 2>(ch, u, v, w, n * E, alpha, beta, normsq);                    \
-    case 3: return launch_grid_chain_step_k<S, E, NS, 3>(ch, u, v, w, n * E, alpha, beta, normsq);                    \
-    default: return launch_grid_chain_step_k<S, E, NS, 4>(ch, u, v, w, n * E, alpha, beta, normsq);                   \
+    case 2: return launch_grid_chain_step_k<S, E, NS, 2>(ch, u, v, w, n * E, alpha, beta, normsq, first_elem, end_elem);                    \
+    case 3: return launch_grid_chain_step_k<S, E, NS, 3>(ch, u, v, w, n * E, alpha, beta, normsq, first_elem, end_elem);                    \
+    default: return launch_grid_chain_step_k<S, E, NS, 4>(ch, u, v, w, n * E, alpha, beta, normsq, first_elem, end_elem);                   \
     }
     switch (op->dtype) {
     case JH_F32: JH_GCS_K(float, 1, 4)
@@ -231,6 +248,18 @@ int grid_chain_step(const jh_chain *ch, void *u, const void *v, void *w, double 
     }
 #undef JH_GCS_K
     return jh_fail(JH_ERR_INVALID, "grid chain step: unknown dtype %d", op->dtype);
+}
+
+int grid_chain_step(const jh_chain *ch, void *u, const void *v, void *w, double alpha, double beta, double *normsq)
+{
+    return grid_chain_step_by_dtype(ch, u, v, w, alpha, beta, normsq, 0, -1);
+}
+
+// positions [first_elem, first_elem + count) of every block: those positions of every u_i, the K pieces w_k[first_elem, first_elem + count), the
+// range's share of ||u||^2 (returned, or with normsq == NULL added to the context's accumulator in enqueue order)
+int grid_chain_step_range(const jh_chain *ch, void *u, const void *v, void *w, double alpha, double beta, int64_t first_elem, int64_t count, double *normsq)
+{
+    return grid_chain_step_by_dtype(ch, u, v, w, alpha, beta, normsq, first_elem, first_elem + count);
 }
 
 }  // namespace jhb

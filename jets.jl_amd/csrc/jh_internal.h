@@ -148,6 +148,8 @@ struct jh_context {
     int64_t grid_chain_step = 0;       // knob: jh_chain_bidiag_step (and the LSQR / CGLS loops of jh_lsqr_solve_chain / jh_cgls_solve_chain) on a FORWARD chain through an N x (2 .. 4) grid in one pass (jh_grid_chain_step.hip): 1 yes, 0 (default) JH_ERR_UNSUPPORTED as before
     int64_t last_grid_chain_step_shape = 0;   // how the most recent grid chain step was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
     int64_t grid_range = 0;            // knob: jh_blockop_mul_adj_range / _normal_mul_range / _bidiag_step_range on an N x (2 .. 4) grid of equal elementwise blocks, the range being positions INSIDE a block (jh_grid_range.hip): 1 yes, 0 (default) JH_ERR_UNSUPPORTED as before
+    int64_t grid_chain_range = 0;      // knob: jh_chain_apply_range (ADJOINT / NORMAL) and jh_chain_bidiag_step_range (with grid_chain_step = 1 as well) on a chain through an N x (2 .. 4) grid, the range being positions INSIDE a block: 1 yes, 0 (default) JH_ERR_UNSUPPORTED as before
+    int64_t last_grid_chain_range_shape = 0;   // how the most recent ranged grid-chain call was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
     int64_t last_grid_range_shape = 0; // how the most recent ranged grid call was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
     int64_t fwd_anchor = -1;           // knob: the tall forward of rows that are not whole packs on lanes anchored to each row's own 16-byte grid (k_tall_fwd_anchored): -1 from 64 KiB rows on, 0 never, 1 always
     int64_t wide_twin = 1;             // knob: wide elementwise operators on their tall twin: 0 never (general kernels), 1 adjoint always + forward from 16 MiB blocks, 2 both always (tests)
@@ -186,6 +188,7 @@ int grid_step_range(const jh_blockop *op, void *u, const void *v, void *w, doubl
 }
 namespace jhb {   // jh_grid_chain_step.hip: the one-pass Golub-Kahan step of a FORWARD chain through an N x (2 .. 4) grid (knob grid_chain_step; the checks are jh_chain_bidiag_step's)
 int grid_chain_step(const jh_chain *ch, void *u, const void *v, void *w, double alpha, double beta, double *normsq);
+int grid_chain_step_range(const jh_chain *ch, void *u, const void *v, void *w, double alpha, double beta, int64_t first_elem, int64_t count, double *normsq);   // knob grid_chain_range as well: positions [first_elem, first_elem + count) of every block
 }
 namespace jhb {   // jh_tall_chain.hip: L' (JH_CHAIN_ADJOINT) / L'L (JH_CHAIN_NORMAL) of a FORWARD chain; the checks of the solvers on a chain (op: its operator)
 int chain_apply_derived(const jh_chain *fwd, int which, jh_bvec *out, const jh_bvec *in);

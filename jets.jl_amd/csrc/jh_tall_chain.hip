@@ -13,6 +13,7 @@ int chain_launch_step(const jh_chain *ch, const ChainArgs &ca, void *u, const vo
 bool grid_chain_ok(const jh_blockop *op);                                                                     // jh_grid_chain.hip
 bool grid_chain_vectors_ok(const jh_blockop *op, const void *a, const void *b);
 int grid_chain_launch(const jh_chain *ch, int prog, int type, void *out, const void *in, int accumulate);   // prog: 0 own, 1 / 2 the derived ADJOINT / NORMAL
+int grid_chain_launch_range(const jh_chain *ch, void *out, const void *in, int accumulate, int64_t first_elem, int64_t count);   // an ADJOINT / NORMAL handle's own program over positions inside a block
 }  // namespace jhb
 
 namespace {
@@ -266,8 +267,20 @@ int jh_chain_apply_range(const jh_chain *ch, jh_bvec *out, const jh_bvec *x, int
     JH_TRY(jh_enter(op, out, x));
     if (ch->type == JH_CHAIN_FORWARD)
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_apply_range: a FORWARD chain needs no exchange (each rank's rows depend on the replicated domain vector alone)");
-    if (ch->ncol > 1) return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_apply_range: a grid chain has no ranged form (apply the whole vector)");
+    // a chain through an N x (2 .. 4) grid (knob grid_chain_range = 1): the range is positions INSIDE a block -- a grid kernel's lane owns one pack position
+    // across all K columns --, the K pieces out_k[first_elem, first_elem + count) are written (k_grid_chain over those lanes, jh_grid_chain_kernels.h)
+    const bool grid = ch->ncol > 1;
+    if (grid && jh_ctx().grid_chain_range != 1)
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_apply_range: a grid chain has no ranged form (apply the whole vector)");
     JH_TRY(chain_check(ch, out, x, accumulate, "jh_chain_apply_range"));
+    if (grid) {
+        JH_TRY(jhb::grid_range_bounds(op, first_elem, count, "jh_chain_apply_range"));
+        if (ch->op_gen != op->table_gen && jhb::stream_is_capturing(jh_ctx().stream))
+            return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_apply_range: the operator was pointed again since the chain's row table was built, and the stream is capturing");
+        if (count == 0) return JH_OK;
+        if (ch->op_gen != op->table_gen) JH_TRY(chain_sync_rows(const_cast<jh_chain *>(ch)));
+        return jhb::grid_chain_launch_range(ch, out->data, x->data, accumulate, first_elem, count);
+    }
     JH_REQUIRE(first_elem >= 0 && count >= 0 && first_elem <= out->length - count,
                "jh_chain_apply_range: elements [%lld, %lld) outside the domain vector (%lld elements)", (long long)first_elem,
                (long long)(first_elem + count), (long long)out->length);
@@ -334,16 +347,36 @@ int jh_chain_bidiag_step_range(const jh_chain *fwd, jh_bvec *u, const jh_bvec *v
 {
     JH_REQUIRE(fwd && u && v && w, "jh_chain_bidiag_step_range: null argument");
     JH_REQUIRE(fwd->type == JH_CHAIN_FORWARD, "jh_chain_bidiag_step_range: needs a FORWARD chain (got type %d)", fwd->type);
-    if (fwd->ncol > 1) return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step_range: a grid chain has no one-pass step (run the FORWARD chain, then the ADJOINT)");
-    if (!fwd->nrm_ok)
-        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step_range: R and R^H need more than %d range-side stages", JH_CHAIN_MAX_STAGES);
     const jh_blockop *op = fwd->op;
     JH_TRY(jh_enter(op, u, v, w));
+    // (the handles' context is entered BEFORE the grid and nrm_ok refusals, which it used to follow: the knobs are per context and must be read in the
+    // handle's.  A call whose handles live in different contexts therefore reports that, where it used to report the grid refusal first.)
+    // a chain through an N x (2 .. 4) grid: knob grid_chain_range = 1, and grid_chain_step = 1 as for the whole-vector step (the rule of the bare grids'
+    // ranged calls: a whole-vector knob also governs the ranged form); the range is positions INSIDE a block (k_grid_chain_step over those lanes)
+    const bool grid = fwd->ncol > 1;
+    if (grid && !(jh_ctx().grid_chain_range == 1 && jh_ctx().grid_chain_step == 1))
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step_range: a grid chain has no one-pass step (run the FORWARD chain, then the ADJOINT)");
+    if (!fwd->nrm_ok)
+        return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step_range: R and R^H need more than %d range-side stages", JH_CHAIN_MAX_STAGES);
     const int64_t nrange = op->row_off[(size_t)op->nrow], ndom = op->col_off[(size_t)op->ncol];
     JH_REQUIRE(u->dtype == op->dtype && v->dtype == op->dtype && w->dtype == op->dtype, "jh_chain_bidiag_step_range: dtype mismatch");
     JH_REQUIRE(u->length == nrange && v->length == ndom && w->length == ndom,
                "jh_chain_bidiag_step_range: u must be a range vector, v and w domain vectors of the operator");
     JH_REQUIRE(w->data != v->data && u->data != v->data && u->data != w->data, "jh_chain_bidiag_step_range: u, v and w must be three vectors");
+    if (grid) {
+        JH_TRY(jhb::grid_range_bounds(op, first_elem, count, "jh_chain_bidiag_step_range"));
+        if (!chain_vectors_ok(fwd, u->data, v->data) || !chain_vectors_ok(fwd, nullptr, w->data))
+            return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step_range: a vector or coefficient array is not aligned like its scalar");
+        if (count == 0) {                                       // (nothing to do -- but the refusals of fwd_ready still come first)
+            if (op->nonlinear && !op->pointed)
+                return jh_fail(JH_ERR_STATE, "jh_chain_bidiag_step_range: operator has nonlinear blocks and no linearisation point (jh_blockop_point)");
+            if (fwd->op_gen != op->table_gen && jhb::stream_is_capturing(jh_ctx().stream))
+                return jh_fail(JH_ERR_UNSUPPORTED, "jh_chain_bidiag_step_range: the operator was pointed again since the chain's row table was built, and the stream is capturing");
+            return JH_OK;
+        }
+        JH_TRY(fwd_ready(fwd, "jh_chain_bidiag_step_range"));
+        return jhb::grid_chain_step_range(fwd, u->data, v->data, w->data, alpha, beta, first_elem, count, normsq);
+    }
     JH_REQUIRE(first_elem >= 0 && count >= 0 && first_elem <= ndom - count,
                "jh_chain_bidiag_step_range: elements [%lld, %lld) outside the domain vector (%lld elements)", (long long)first_elem,
                (long long)(first_elem + count), (long long)ndom);

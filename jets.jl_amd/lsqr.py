@@ -338,7 +338,7 @@ class _TeamEngine:
     def __init__(self, T):
         self.T = T
         self.team = T.team
-        self._tmp_d = None
+        self._tmp_d = self._tmp_q = None
         self._engines = [_Engine(A) for A in T.local_ops]     # per member: the fused local halves
         self.fused_step = os.environ.get("JETS_LSQR_FUSED_STEP", "1") != "0"
         # members that are weighted chains (W_k o A_k, ...): the ranged chain step and the ranged NORMAL chain of rowpart.TeamOp
@@ -351,8 +351,15 @@ class _TeamEngine:
         return self.chain_step and self.fused_step and getattr(self, "normal", None) is not None
 
     def _normal(self, y, p) -> float:
-        """y = L'L p summed over the members (TeamOp.normal_mul_); returns <p, y> on member 0's replica."""
-        self.T.normal_mul_(y, p)
+        """y = L'L p summed over the members (TeamOp.fused_normal_mul_: the ranged NORMAL chains); returns <p, y> on member 0's replica."""
+        if not self.T.fused_normal_mul_(y, p):
+            # (members whose chains run through grids, the ranged NORMAL chain declined before anything was enqueued -- the knob grid_chain_range back
+            # at 0 under this engine: A then A' through a range vector, what cgnr_core does without the hook)
+            if self._tmp_q is None:
+                self._tmp_q = self.zeros_rng()
+            qn = self.fwd(self._tmp_q, p, 1.0, 0.0)
+            self.adj(y, self._tmp_q, 1.0, 0.0)
+            return qn * qn
         from . import device as _device
 
         _device.context_use(self.team.contexts[0])

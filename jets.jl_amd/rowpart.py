@@ -165,8 +165,9 @@ class RowPartitionedOp:
 
     @property
     def fused_normal(self) -> bool:
-        """normal_mul_ needs no range temporary: a weighted shard (L = W_loc o A_loc, ...) applies L'L as one fused NORMAL chain."""
-        return self._local_normal is not None
+        """normal_mul_ needs no range temporary: a weighted shard (L = W_loc o A_loc, ...) applies L'L as one fused NORMAL chain.  Read per
+        application: a run through a grid exists only while the knob grid_chain_range is 1 (_ShardChains.has_normal)."""
+        return self._local_normal is not None and (self._chains is None or self._chains.has_normal)
 
     @property
     def chain_step(self) -> bool:
@@ -205,7 +206,7 @@ class RowPartitionedOp:
         if self._pipelined_normal is not None and (self.comm.world > 1 or force_collective):
             if self._pipelined_normal(y, self.local_op, m):
                 return True
-        if pipelined_only or self._local_normal is None:
+        if pipelined_only or not self.fused_normal:
             return False
         self._local_normal(y, self.local_op, m)
         self.comm.all_reduce_sum_(y, force=force_collective)
@@ -251,7 +252,7 @@ class RowPartitionedOp:
 class _ShardChains:
     """The fused chains of a WEIGHTED shard: a local operator L that the chain planner (chains.py) turns into one run around the shard's
     tall operator -- W_loc o A_loc (W_loc = JopDiagonal of this rank's rows of the weights), a block-diagonal @blockop of weights o A_loc,
-    W o A o M, a * (W o A).  adjoint(L) is one ADJOINT chain, adjoint(L) o L one NORMAL chain (W' and W read one coefficient stream:
+    W o A o M, a * (W o A); with the knob grid_chain_range = 1 also around a native N x (2 .. 4) grid of equal blocks.  adjoint(L) is one ADJOINT chain, adjoint(L) o L one NORMAL chain (W' and W read one coefficient stream:
     jh_chain_create's dedupe), L itself one FORWARD chain whose Golub-Kahan step runs range by range (jh_chain_bidiag_step_range: LSQR / CGLS
     on the shard; JETS_CHAIN_STEP=0 keeps the chain into a range temporary, as chains.SolverChains does on one GPU).  Planned here once; the handles live in this object's cache until close().  A bare block operator is not
     weighted: plain shards keep their routes (jh_blockop_*_range)."""
@@ -272,20 +273,67 @@ class _ShardChains:
             self._nrm = _chn.stages_of(self._nrm_op)
             if os.environ.get("JETS_CHAIN_STEP", "1") != "0":
                 self._fwd = _chn.stages_of(L)
-        self.has_adj = self._adj is not None and _chn.one_run(self._adj, self.cache, "rowpart_adj", _chn.CHAIN_ADJOINT, make=False, grid=False) is not None
-        self.has_normal = self._nrm is not None and _chn.one_run(self._nrm, self.cache, "rowpart_normal", _chn.CHAIN_NORMAL, make=False, grid=False) is not None
-        self.has_step = self._fwd is not None and _chn.one_run(self._fwd, self.cache, "rowpart_fwd", _chn.CHAIN_FORWARD, make=False, grid=False) is not None
+        # the block length when the operator inside L is a device-native N x (2 .. 4) grid of equal blocks: its chains' ranged calls take positions
+        # inside a block (knob grid_chain_range, read per application: has_adj / has_normal / has_step), the ranges are cut over it
+        self.grid_n = None
+        self._has_adj = self._planned(self._adj, "rowpart_adj", _chn.CHAIN_ADJOINT)
+        self._has_normal = self._planned(self._nrm, "rowpart_normal", _chn.CHAIN_NORMAL)
+        self._has_step = self._planned(self._fwd, "rowpart_fwd", _chn.CHAIN_FORWARD)
+
+    def _planned(self, stages, tag, ctype) -> bool:
+        """Is the stage list one fused run -- around a tall operator, or through a grid of equal blocks (then grid_n is its block length)?"""
+        anchor = None if stages is None else self._chn.run_anchor(stages, self.cache, tag, ctype)
+        if anchor is None:
+            return False
+        if anchor.kind != "grid":
+            return True
+        n = _grid_block_len(anchor.base)
+        if n is None:
+            return False
+        self.grid_n = n
+        return True
+
+    def _grid_on(self, step: bool = False) -> bool:
+        """A tall run: yes.  A run through a grid: does the library take its ranged form in the CURRENT context (knob grid_chain_range = 1, the
+        default is 0: no grid chain is planned, the shard keeps its previous routes call for call; the step needs grid_chain_step = 1 as well)?"""
+        if self.grid_n is None:
+            return True
+        return _grid_chain_range_on() and (not step or self._chn.grid_step_enabled())
+
+    @property
+    def has_adj(self) -> bool:
+        return self._has_adj and self._grid_on()
+
+    @property
+    def has_normal(self) -> bool:
+        return self._has_normal and self._grid_on()
+
+    @property
+    def has_step(self) -> bool:
+        return self._has_step and self._grid_on(step=True)
+
+    @has_step.setter
+    def has_step(self, value: bool):
+        self._has_step = bool(value)
+
+    @property
+    def normal_planned(self) -> bool:
+        """adjoint(L) o L is one fused run, whatever the knobs say now (has_normal says whether it may run in the current context)."""
+        return self._has_normal
+
+    def _one_run(self, stages, tag, ctype):
+        return self._chn.one_run(stages, self.cache, tag, ctype, grid=self.grid_n is not None)
 
     def adjoint(self):
         """The ChainHandle of adjoint(L), or None (not one run; the library declined)."""
-        return self._chn.one_run(self._adj, self.cache, "rowpart_adj", self._chn.CHAIN_ADJOINT) if self.has_adj else None
+        return self._one_run(self._adj, "rowpart_adj", self._chn.CHAIN_ADJOINT) if self.has_adj else None
 
     def normal(self):
-        return self._chn.one_run(self._nrm, self.cache, "rowpart_normal", self._chn.CHAIN_NORMAL) if self.has_normal else None
+        return self._one_run(self._nrm, "rowpart_normal", self._chn.CHAIN_NORMAL) if self.has_normal else None
 
     def step(self):
         """The FORWARD ChainHandle of L (its ranged Golub-Kahan step: ChainHandle.bidiag_step_range), or None."""
-        return self._chn.one_run(self._fwd, self.cache, "rowpart_fwd", self._chn.CHAIN_FORWARD, grid=False) if self.has_step else None
+        return self._one_run(self._fwd, "rowpart_fwd", self._chn.CHAIN_FORWARD) if self.has_step else None
 
     def local_normal(self, y, L, m):
         """y = L'L m on this rank's rows: the whole-vector NORMAL chain (the stage-by-stage chain when the library declines it)."""
@@ -318,7 +366,7 @@ def for_device(part: RowPartition, local_op, comm=None) -> RowPartitionedOp:
     sc = _ShardChains(local_op)
     routes = {} if xch is None else _pipelined_routes(xch, local_op, sc)
     return RowPartitionedOp(part, local_op, comm, lambda d, A, m: mul_(d, A, m), lambda m, A, d: mul_(m, adjoint(A), d), dot, norm,
-                            local_normal=sc.local_normal if sc.has_normal else None, chains=sc, grid_n=_grid_block_len(local_op), **routes)
+                            local_normal=sc.local_normal if sc.normal_planned else None, chains=sc, grid_n=_grid_block_len(local_op), **routes)
 
 
 class _TorchExchange:
@@ -411,6 +459,13 @@ def _grid_range_on() -> bool:
     return tune_get("grid_range") == 1
 
 
+def _grid_chain_range_on() -> bool:
+    """Does the library take the ranged calls of a chain through a grid in the CURRENT context (knob grid_chain_range; the default is 0)?"""
+    from .device import tune_get
+
+    return tune_get("grid_chain_range") == 1
+
+
 def _grid_block_len(A):
     """The block length n of a device-native N x (2 .. 4) grid of equal blocks, else None: a property of the operator, worked out once where
     the routes are built (it walks the N K children).  Whether the ranged calls take such a grid is the knob's to say (_grid_range_on, read
@@ -496,10 +551,11 @@ def _pipelined_routes(xch, local_op, sc) -> dict:
 
     def weighted(out, x, h):
         """A weighted shard's ADJOINT / NORMAL chain range by range (jh_chain_apply_range, accumulate 0: with +-1 every rank would add `out`
-        once).  False when there is no handle."""
+        once).  False when there is no handle.  A chain through a grid (knob grid_chain_range = 1): the ranges are positions inside a block, a
+        finished range goes out as its K pieces."""
         if nchunks <= 1 or not xch.ready() or h is None:
             return False
-        return _pipelined(xch, out, nchunks, lambda lo, cnt: h.apply_range(out, x, lo, cnt, 0))
+        return _pipelined(xch, out, nchunks, lambda lo, cnt: h.apply_range(out, x, lo, cnt, 0), grid_n=h.block_len)
 
     def pipelined_adj(m, A, d):
         """Local adjoint in `nchunks` element ranges (jh_blockop_mul_adj_range), each range's all-reduce under the next range's kernel.
@@ -529,7 +585,7 @@ def _pipelined_routes(xch, local_op, sc) -> dict:
             if h is None:
                 return None
             check(lib.jh_normsq_reset())
-            r = _pipelined(xch, w, nchunks, lambda lo, cnt: h.bidiag_step_range(u, v, w, alpha, beta, lo, cnt), finish=xch.normsq)
+            r = _pipelined(xch, w, nchunks, lambda lo, cnt: h.bidiag_step_range(u, v, w, alpha, beta, lo, cnt), finish=xch.normsq, grid_n=h.block_len)
             if r is None:                                     # the library declined before anything was touched (R + R^H above four stages): for good
                 sc.has_step = False
             return r
@@ -675,6 +731,11 @@ class TeamOp:
         # members that are N x (2 .. 4) grids of equal blocks of ONE length: the ranges are cut over it when the knob grid_range is 1 (_team_grid_n)
         lens = {_grid_block_len(A) for A in self.local_ops}
         self._grid_n = lens.pop() if len(lens) == 1 else None
+        # weighted members whose chains run through grids: of ONE block length, or the ranged chain routes decline (a grid handle reads a range as
+        # positions inside its block: flat ranges, or another member's block length, are not its ranges)
+        clens = {None if sc is None else sc.grid_n for sc in self._chains}
+        self._chain_grids = clens != {None}
+        self._chain_grids_mixed = self._chain_grids and len(clens) > 1
 
     def _team_grid_n(self):
         """The block length to cut the ranges over, or None (the flat domain).  Knobs are per context: grid_range is read in EVERY member's
@@ -686,15 +747,39 @@ class TeamOp:
             raise ValueError(f"knob grid_range differs between the team's contexts ({[int(v) for v in on]}): set it in every member's context")
         return self._grid_n if on[0] else None
 
+    def _team_chain_grid_n(self, step: bool = False):
+        """Weighted members whose chains run through grids of ONE block length: that length when the knob grid_chain_range is 1 (the step: and
+        grid_chain_step), else None.  The knobs are read in EVERY member's context; members that disagree are an error here, before any member's
+        kernel has touched its u."""
+        if not self._chain_grids or self._chain_grids_mixed:
+            return None
+        n = self._chains[0].grid_n
+        for name, on in (("grid_chain_range", [_grid_chain_range_on() for _ in self.team.each()]),
+                         ("grid_chain_step", [self._chains[0]._chn.grid_step_enabled() for _ in self.team.each()] if step else [True])):
+            if any(on) and not all(on):
+                raise ValueError(f"knob {name} differs between the team's contexts ({[int(v) for v in on]}): set it in every member's context")
+            if not on[0]:
+                return None
+        return n
+
+    def _every_member(self, attr: str) -> bool:
+        """Does every member's _ShardChains have `attr` (has_adj / has_normal / has_step)?  Chains through grids read their knobs: each member's in
+        ITS context (knobs are per context); members of mixed kinds or block lengths have no common ranges."""
+        if any(sc is None for sc in self._chains) or self._chain_grids_mixed:
+            return False
+        if not self._chain_grids:
+            return all(getattr(sc, attr) for sc in self._chains)
+        return all([getattr(self._chains[k], attr) for k, _ in self.team.each()])
+
     @property
     def chain_step(self) -> bool:
         """Every member is a weighted chain with a ranged one-pass step (jh_chain_bidiag_step_range)."""
-        return all(sc is not None and sc.has_step for sc in self._chains)
+        return self._every_member("has_step")
 
     @property
     def fused_normal(self) -> bool:
         """Every member is a weighted chain whose normal operator is one NORMAL chain (jh_chain_apply_range): normal_mul_ needs no `tmp`."""
-        return all(sc is not None and sc.has_normal for sc in self._chains)
+        return self._every_member("has_normal")
 
     def _member_handles(self, which: str):
         """Every member's chain handle (`step` / `normal` of its _ShardChains), each built in its own context; None when one is missing."""
@@ -760,7 +845,7 @@ class TeamOp:
 
         # members that are N x (2 .. 4) grids (knob grid_range = 1): ranges of positions inside a block, a finished range's K pieces exchanged
         # (a group per piece: a group holds one collective per member)
-        grid_n = self._team_grid_n() if native else None
+        grid_n = self._team_grid_n() if native else self._team_chain_grid_n()
         bounds = _chunk_bounds(m[0].length(), self.nchunks) if grid_n is None else _grid_chunk_bounds(grid_n, self.nchunks)
         pieces = (0,) if grid_n is None else [k * grid_n for k in builtins.range(m[0].length() // grid_n)]
         for lo, cnt in bounds:
@@ -776,12 +861,35 @@ class TeamOp:
             check(lib.jh_comm_join())
         return True
 
+    def _ranged_chains(self, out: TeamVec, enqueue_range) -> bool:
+        """_ranged over the members' chains.  False when the library declines on the first range of member 0, before anything is touched (a
+        grid chain with the knob grid_chain_range back at 0): the caller takes its previous route.  A decline after that raises."""
+        from ._ffi import JetsHipError
+
+        done = [0]
+
+        def counted(k, lo, cnt):
+            enqueue_range(k, lo, cnt)
+            done[0] += 1
+
+        try:
+            return self._ranged(out, counted, native=False)
+        except JetsHipError as e:
+            if e.status == 4 and done[0] == 0 and any(sc is not None and sc.grid_n is not None for sc in self._chains):
+                return False
+            raise
+
     def mul_adj_(self, m: TeamVec, d: TeamVec) -> TeamVec:
         from ._ffi import lib, check, JetsHipError
         from .jets import mul_, adjoint
 
         if self.one_call and self._team_call(lib.jh_team_mul_adj, m, d, self.nchunks):
             return m
+        # weighted members whose chains run through grids (knob grid_chain_range = 1): adjoint(L_k) as ONE ADJOINT chain per member and range
+        if self._team_chain_grid_n() is not None and self._every_member("has_adj"):
+            hs = self._member_handles("adjoint")
+            if hs is not None and self._ranged_chains(m, lambda k, lo, cnt: hs[k].apply_range(m[k], d[k], lo, cnt, 0)):
+                return m
         try:
             if self._ranged(m, lambda k, lo, cnt: check(lib.jh_blockop_mul_adj_range(self._natives[k].handle, m[k].handle, d[k].handle, lo, cnt))):
                 return m
@@ -801,11 +909,8 @@ class TeamOp:
         are weighted chains (W_k o A_k, ...) apply L_k'L_k as one NORMAL chain per range (jh_chain_apply_range) and need no `tmp`."""
         from ._ffi import lib, check, JetsHipError
 
-        if self.fused_normal:                                  # weighted members: L_k'L_k m as ONE NORMAL chain per member and range
-            hs = self._member_handles("normal")
-            if hs is not None:
-                self._ranged(y, lambda k, lo, cnt: hs[k].apply_range(y[k], m[k], lo, cnt, 0), native=False)
-                return y
+        if self.fused_normal_mul_(y, m):
+            return y
         if self.one_call and self._team_call(lib.jh_team_normal_mul, y, m, self.nchunks):
             return y
         try:
@@ -818,6 +923,15 @@ class TeamOp:
             raise ValueError("normal_mul_: this operator has no fused A'A; pass tmp (a range-side TeamVec)")
         return self.mul_adj_(y, self.mul_(tmp, m))
 
+    def fused_normal_mul_(self, y: TeamVec, m: TeamVec) -> bool:
+        """normal_mul_ where it needs no range temporary: weighted members' L_k'L_k m as ONE NORMAL chain per member and range.  False -- nothing
+        enqueued, y untouched -- when the members have no such chains (chains through grids: the knob grid_chain_range at 0 in their contexts) or the
+        library declines the first range: the caller then applies A and A' through a range vector."""
+        if not self.fused_normal:
+            return False
+        hs = self._member_handles("normal")
+        return hs is not None and self._ranged_chains(y, lambda k, lo, cnt: hs[k].apply_range(y[k], m[k], lo, cnt, 0))
+
     def bidiag_step_(self, u: TeamVec, v: TeamVec, w: TeamVec, alpha: float, beta: float):
         """One Golub-Kahan step on every member (jh_blockop_bidiag_step_range per range; weighted members: jh_chain_bidiag_step_range) with the ranged exchange of w;
         returns the GLOBAL ||u||^2 -- the host adds the members' deferred accumulators -- or None without a ranged kernel."""
@@ -826,6 +940,7 @@ class TeamOp:
         from ._ffi import lib, check, JetsHipError
 
         hs = None
+        self._team_chain_grid_n(step=True)                     # (weighted grid members: knobs that differ between the contexts raise here, before any u changes)
         if self.chain_step:                                    # weighted members: jh_chain_bidiag_step_range per member and range
             hs = self._member_handles("step")
             if hs is None:
