@@ -213,9 +213,10 @@ def test_ranged_grid_chains_have_the_bits_of_the_whole_vector_calls(Jets, oracle
 @pytest.mark.parametrize("name", [k for k in CONFIGS if k != "W o A"])
 def test_stage_lists_and_grids_of_several_kinds(Jets, oracle, dt, mixed, name):
     """NW = 0 / 2, a domain-side diagonal, a scalar stage; plain diagonals, and a grid with adjointed diagonals, zero blocks (a whole row of them),
-    identities and scalar blocks."""
+    identities and scalar blocks -- each also against the oracle's stage-by-stage result, so that a term the ranged and the whole-vector kernel got
+    wrong in the same way would show."""
     rig = GridRig(Jets, oracle, dt, NROW, 4, 515, mixed=True) if mixed else GridRig(Jets, oracle, dt, NROW, 3, 515)
-    _run_config(Jets, oracle, rig, CONFIGS[name], (0, -2), (-0.5,), with_oracle=False)
+    _run_config(Jets, oracle, rig, CONFIGS[name], (0, -2), (-0.5,), with_oracle=True)
     rig.close()
 
 

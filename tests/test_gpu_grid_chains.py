@@ -28,11 +28,12 @@ class GridRig:
     """An N x K grid A (blocks of n elements) with two weight vectors on its range, two diagonals on its domain (K n elements) and a block-diagonal
     block operator of weights, on the device and in the oracle.  Chains are token lists in APPLICATION order as in tests/test_gpu_chains.py.
     data(tag, n): host arrays in place of the counter generator's U[0,1) streams -- tag ("A", i, j) the coefficients of block (i, j), ("w", k) the
-    k-th weights (nrow * n elements), ("c", k) the k-th domain diagonal (ncol * n elements)."""
+    k-th weights (nrow * n elements), ("c", k) the k-th domain diagonal (ncol * n elements).  kinds: the blocks' kinds (nrow lists of ncol names),
+    overriding `mixed`; with_wb=False: no block-diagonal weight operator (nrow^2 children) is built.  The token ("Wb", 0, True) is its adjoint."""
 
-    def __init__(self, J, oracle, dt, nrow, ncol, n, mixed=False, seed=53, data=None):
+    def __init__(self, J, oracle, dt, nrow, ncol, n, mixed=False, seed=53, data=None, kinds=None, with_wb=True):
         self.J, self.o, self.dt, self.nrow, self.ncol, self.n = J, oracle, dt, nrow, ncol, n
-        self.A, self.ora = _mixed_ops(J, oracle, dt, _grid_kinds(nrow, ncol, mixed), [n] * nrow, [n] * ncol, seed=seed,
+        self.A, self.ora = _mixed_ops(J, oracle, dt, kinds or _grid_kinds(nrow, ncol, mixed), [n] * nrow, [n] * ncol, seed=seed,
                                       coeff=None if data is None else (lambda i, j, nr: data(("A", i, j), nr)))
         R, D = J.range(self.A), J.domain(self.A)
         if data is None:
@@ -47,7 +48,7 @@ class GridRig:
         self.M = [J.JopDiagonal(c) for c in self.c]
         spc = J.JetSpace(dt, n)
         rows = []
-        for i in range(nrow):
+        for i in range(nrow if with_wb else 0):
             row = [J.JopZeroBlock(spc, spc) for _ in range(nrow)]
             if i % 4 == 3:
                 row[i] = J.JopIdentity(spc)
@@ -55,7 +56,7 @@ class GridRig:
                 d = J.JopDiagonal(self.w[0].arrays[i])
                 row[i] = d.H if i % 3 == 1 else d
             rows.append(row)
-        self.Wb = J.blockop(rows)
+        self.Wb = J.blockop(rows) if with_wb else None
 
     def op(self, tok):
         J = self.J
@@ -68,7 +69,7 @@ class GridRig:
         if tok[0] == "M":
             return self.M[tok[1]].H if tok[2] else self.M[tok[1]]
         if tok[0] == "Wb":
-            return self.Wb
+            return self.Wb.H if len(tok) > 2 and tok[2] else self.Wb
         if tok[0] == "s":
             spc = J.range(self.A) if tok[2] == "r" else J.domain(self.A)
             return J.JopLn(dom=spc, rng=spc, df=J.constdiag_df, df_adj=J.constdiag_df_adj, s={"a": tok[1]})
@@ -97,7 +98,8 @@ class GridRig:
                     if i % 4 == 3:
                         nxt.append(np.zeros(n, dt) + b)
                     else:
-                        nxt.append(np.zeros(n, dt) + o.child_mul(o.Block("diag", n, coeff=self.hw[0][i], adjoint=(i % 3 == 1)), np.zeros(n, dt), b))
+                        adj = (i % 3 == 1) != bool(len(tok) > 2 and tok[2])
+                        nxt.append(np.zeros(n, dt) + o.child_mul(o.Block("diag", n, coeff=self.hw[0][i], adjoint=adj), np.zeros(n, dt), b))
                 cur = nxt
             elif tok[0] == "s":
                 cur = o.barr_lincomb([np.empty(n, dt) for _ in cur], [tok[1]], [cur])
@@ -107,7 +109,8 @@ class GridRig:
 
     def close(self):
         self.J.close(self.A)
-        self.J.close(self.Wb)
+        if self.Wb is not None:
+            self.J.close(self.Wb)
 
 
 CHAINS = {
