@@ -211,7 +211,9 @@ int jh_hadamard(jh_bvec *dst, const jh_bvec *x, const jh_bvec *y, int conj_x);
  * `expr` is a C expression over x0..x{nvec-1} (the elements of the vector operands, type T), s0..s{nscal-1} (scalars of
  * type T) and literals -- what the host language prints from its broadcast tree (Julia: a Broadcasted{BlockArrayStyle}),
  * e.g. "s0*x0 + x1/x2" or "exp(-abs2(x0)) * conj(x1)".  Available: + - * /, the HIP math library (exp, log, sqrt, sin, cos,
- * tanh, pow, fmin, fmax, ...), and conj/real/imag/abs/abs2/sign; complex T has + - * / conj abs abs2 exp.  It is compiled once
+ * tanh, pow, ...), conj/real/imag/abs/abs2/sign and jl_max/jl_min -- Julia's max / min: NaN if either operand is, max(-0.0, 0.0) = 0.0;
+ * a raw fmax / fmin stays C's, which drops a NaN operand; sign(x) is x for NaN and +-0 --; complex T has + - * / (the quotient scaled: no
+ * overflow in |w|^2) conj real imag abs abs2 exp, every other function is refused for it when the expression is compiled.  It is compiled once
  * per (expr, dtype, nvec, nscal) with hiprtc for gfx950 -- the device-side twin of Julia compiling the broadcast kernel -- with
  * -ffp-contract=off, so every operation is rounded as written (no FMA): for + - * / the result has the bits of the reference's
  * CPU broadcast.  Programs are cached for the life of the context.  jh_bcast_check only compiles (no device needed).

@@ -194,16 +194,20 @@ def assign_(dst: _DevVec, expr) -> _DevVec:
 
 
 class _Funcs:
-    """Elementwise functions for lazy expressions: Jets.bc.exp(x), Jets.bc.maximum(x, y), ..."""
+    """Elementwise functions for lazy expressions: Jets.bc.exp(x), Jets.bc.maximum(x, y), ...  `unary` names are emitted as they are; `binary`
+    maps a name to the device function it emits.  maximum / minimum are Julia's max / min (NaN if either operand is NaN, max(-0.0, 0.0) = 0.0,
+    min(0.0, -0.0) = -0.0: jl_max / jl_min of the kernels' prelude), not C's fmax / fmin, which drop a NaN operand.  Which names exist for complex
+    elements (exp abs abs2 conj real imag) and which are refused when the expression is compiled: the table in README.md."""
+
+    unary = ("exp", "log", "sqrt", "sin", "cos", "tan", "tanh", "sinh", "cosh", "abs", "abs2", "conj", "real", "imag", "sign",
+             "floor", "ceil", "log2", "log10", "exp2", "atan", "asin", "acos", "erf")
+    binary = {"maximum": "jl_max", "minimum": "jl_min", "pow": "pow", "atan2": "atan2", "hypot": "hypot"}
 
     def __getattr__(self, name):
-        unary = {"exp", "log", "sqrt", "sin", "cos", "tan", "tanh", "sinh", "cosh", "abs", "abs2", "conj", "real", "imag", "sign",
-                 "floor", "ceil", "log2", "log10", "exp2", "atan", "asin", "acos", "erf"}
-        binary = {"maximum": "fmax", "minimum": "fmin", "pow": "pow", "atan2": "atan2", "hypot": "hypot"}
-        if name in unary:
+        if name in self.unary:
             return lambda x: BExpr._join(name + "({})", x)
-        if name in binary:
-            return lambda x, y: BExpr._join(binary[name] + "({}, {})", x, y)
+        if name in self.binary:
+            return lambda x, y: BExpr._join(self.binary[name] + "({}, {})", x, y)
         raise AttributeError(name)
 
 

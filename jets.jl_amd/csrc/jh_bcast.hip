@@ -69,11 +69,32 @@ template <typename R1, typename R2> __device__ inline cx<CXW_> operator*(cx<R1> 
     typedef CXW_ W;
     return cx<W>((W)a.re * (W)b.re - (W)a.im * (W)b.im, (W)a.re * (W)b.im + (W)a.im * (W)b.re);
 }
+// Julia's complex / is scaled (exact to a few ulp wherever the quotient is representable); the textbook b.re^2 + b.im^2 overflows or flushes for
+// |b| beyond the square root of the range.  Both operands are brought to [1, 2) by a power of two taken from their larger part (exact), the
+// textbook formula runs there (den in [1, 8); a part more than half the exponent range below the other drops out, far under the rounding error
+// of the quotient's norm) and the exponents come back with one ldexp per part (overflow and gradual underflow are the final rounding's).
+// A zero or non-finite larger part keeps the plain formula's Inf / NaN.
 template <typename R1, typename R2> __device__ inline cx<CXW_> operator/(cx<R1> a, cx<R2> b)
 {
     typedef CXW_ W;
-    const W den = (W)b.re * (W)b.re + (W)b.im * (W)b.im;
-    return cx<W>(((W)a.re * (W)b.re + (W)a.im * (W)b.im) / den, ((W)a.im * (W)b.re - (W)a.re * (W)b.im) / den);
+    W ar = (W)a.re, ai = (W)a.im, br = (W)b.re, bi = (W)b.im;
+    const W mb = fmax(fabs(br), fabs(bi)), ma = fmax(fabs(ar), fabs(ai));
+    int shift = 0;
+    if (mb > (W)0 && mb < (W)__builtin_inf()) {            // finite and nonzero (a NaN fails both)
+        const int eb = ilogb(mb);
+        br = ldexp(br, -eb);
+        bi = ldexp(bi, -eb);
+        shift = -eb;
+        if (ma > (W)0 && ma < (W)__builtin_inf()) {
+            const int ea = ilogb(ma);
+            ar = ldexp(ar, -ea);
+            ai = ldexp(ai, -ea);
+            shift += ea;
+        }
+    }
+    const W den = br * br + bi * bi;
+    const W qr = (ar * br + ai * bi) / den, qi = (ai * br - ar * bi) / den;
+    return shift ? cx<W>(ldexp(qr, shift), ldexp(qi, shift)) : cx<W>(qr, qi);
 }
 #undef CXW_
 // real (x) complex, part by part (Julia's a::Real * z): any arithmetic type; an integer takes the complex operand's precision, a double widens it
@@ -92,7 +113,8 @@ template <typename R> __device__ inline R real(cx<R> a) { return a.re; }
 template <typename R> __device__ inline R imag(cx<R> a) { return a.im; }
 template <typename R> __device__ inline R abs2(cx<R> a) { return a.re * a.re + a.im * a.im; }
 template <typename R> __device__ inline R abs(cx<R> a) { return hypot(a.re, a.im); }
-template <typename R> __device__ inline cx<R> exp(cx<R> a) { const R e = exp(a.re); return cx<R>(e * cos(a.im), e * sin(a.im)); }
+// Julia: exp(complex(x, +-0)) = complex(exp(x), +-0) -- no Inf * 0 = NaN in the imaginary part when exp(x) overflows
+template <typename R> __device__ inline cx<R> exp(cx<R> a) { const R e = exp(a.re); return a.im == (R)0 ? cx<R>(e, a.im) : cx<R>(e * cos(a.im), e * sin(a.im)); }
 __device__ inline float conj(float a) { return a; }
 __device__ inline double conj(double a) { return a; }
 __device__ inline float real(float a) { return a; }
@@ -101,8 +123,24 @@ __device__ inline float imag(float) { return 0.f; }
 __device__ inline double imag(double) { return 0.0; }
 __device__ inline float abs2(float a) { return a * a; }
 __device__ inline double abs2(double a) { return a * a; }
-__device__ inline float sign(float a) { return (a > 0.f) - (a < 0.f); }
-__device__ inline double sign(double a) { return (a > 0.0) - (a < 0.0); }
+// Julia's sign: +-1, and the argument itself for +-0 and NaN
+__device__ inline float sign(float a) { return a > 0.f ? 1.f : a < 0.f ? -1.f : a; }
+__device__ inline double sign(double a) { return a > 0.0 ? 1.0 : a < 0.0 ? -1.0 : a; }
+// Julia's max / min (what bc.maximum / bc.minimum and the Julia binding's max / min emit; C's fmax / fmin DROP a NaN operand and leave the sign
+// of a zero open): NaN if either operand is; max(-0, +0) = +0, min(+0, -0) = -0 -- among zeros the sum has max's sign, the negated sum of the
+// negated operands min's.  Real operands only, of either precision or an integer literal (the wider type's result)
+template <typename A, typename B> __device__ inline typename en_<is_num_<A>::v && is_num_<B>::v, typename wd_<A, B>::t>::t jl_max(A a, B b)
+{
+    typedef typename wd_<A, B>::t W;
+    const W x = (W)a, y = (W)b;
+    return (x != x || y != y) ? x + y : x > y ? x : y > x ? y : x == (W)0 ? x + y : x;
+}
+template <typename A, typename B> __device__ inline typename en_<is_num_<A>::v && is_num_<B>::v, typename wd_<A, B>::t>::t jl_min(A a, B b)
+{
+    typedef typename wd_<A, B>::t W;
+    const W x = (W)a, y = (W)b;
+    return (x != x || y != y) ? x + y : x < y ? x : y < x ? y : x == (W)0 ? -((-x) + (-y)) : x;
+}
 )SRC";
 
 std::string build_source(const std::string &expr, int dtype, int nvec, int nscal, int real_mask, int wide_mask)

@@ -352,7 +352,7 @@ Base.similar(bc::Broadcast.Broadcasted{HipStyle{N}}, ::Type{T}) where {N,T} = si
 
 const _cfun = Dict{Any,String}(+ => "+", - => "-", * => "*", / => "/", exp => "exp", log => "log", sqrt => "sqrt", sin => "sin",
                                cos => "cos", tanh => "tanh", abs => "abs", abs2 => "abs2", conj => "conj", real => "real",
-                               imag => "imag", sign => "sign", max => "fmax", min => "fmin")
+                               imag => "imag", sign => "sign", max => "jl_max", min => "jl_min")
 function _emit(x::DevVec, vecs, scals)
     i = findfirst(v -> v === x, vecs)
     i === nothing && (push!(vecs, x); i = length(vecs))

@@ -4,6 +4,14 @@ kernels (jh_bcast_*).  Re-encodes test/runtests.jl:553-600 (a*u .+ b*v .+ c*w, y
 Bar: + - * / and sqrt on real eltypes are BIT-EXACT against numpy evaluating the same operations in the same order and
 type (every operation rounded as written, no FMA); transcendental functions within 2e-6 (Float32) / 1e-14 (Float64)
 relative; complex arithmetic within 1e-6 / 1e-14.
+
+tests/test_gpu_broadcast_functions.py holds the same bars over each function's WHOLE domain against a 50-digit reference (relative error
+alone where the result is a normal number; class and sign where it is zero, subnormal, Inf or NaN), and these guarantees: floor ceil abs abs2
+conj real imag sign max min are bit-exact too, subnormals included; `bc.maximum` / `bc.minimum` (jl_max / jl_min) and `sign` are Julia's --
+max(NaN, x) = max(x, NaN) = NaN, max(-0.0, 0.0) = 0.0, min(0.0, -0.0) = -0.0, sign(NaN) = NaN, sign(+-0.0) = +-0.0 -- while the raw
+fmax / fmin of the case below stay C's; complex z / w is scaled and holds its bar for |z|, |w| anywhere in the exponent range;
+exp(complex(x, +-0.0)) = complex(exp(x), +-0.0) also where exp(x) overflows; the 16-byte, one-element-per-lane and batched kernels give one
+expression the same bits.
 """
 import numpy as np
 import pytest
