@@ -936,165 +936,35 @@ int jh_tune_set(const char *name, int64_t value)
     JH_REQUIRE(name, "jh_tune_set: null name");
     jh_context &c = jh_ctx();
     auto one_of = [&](std::initializer_list<int64_t> ok) { for (int64_t v : ok) if (v == value) return true; return false; };
-    if (!strcmp(name, "fwd_group")) { JH_REQUIRE(value >= 0 && value <= 65536, "fwd_group out of range"); c.fwd_group = value; }
-    else if (!strcmp(name, "fwd_unroll")) { JH_REQUIRE(one_of({0, 1, 2, 4, 8}), "fwd_unroll must be 0 (auto), 1, 2, 4 or 8"); c.fwd_unroll = value; }
-    else if (!strcmp(name, "fwd_wg")) { JH_REQUIRE(one_of({0, 256, 512, 1024}), "fwd_wg must be 0 (auto), 256, 512 or 1024"); c.fwd_wg = value; }
-    else if (!strcmp(name, "adj_unroll")) { JH_REQUIRE(one_of({0, 1, 2, 4}), "adj_unroll must be 0 (auto), 1, 2 or 4"); c.adj_unroll = value; }
-    else if (!strcmp(name, "adj_depth")) { JH_REQUIRE(one_of({0, 1, 2, 4, 8}), "adj_depth must be 0 (auto), 1, 2, 4 or 8"); c.adj_depth = value; }
-    else if (!strcmp(name, "adj_wg")) { JH_REQUIRE(one_of({0, 256, 512, 1024}), "adj_wg must be 0 (auto), 256, 512 or 1024"); c.adj_wg = value; }
-    else if (!strcmp(name, "fwd_order")) { JH_REQUIRE(value >= -1 && value <= 65536, "fwd_order must be -1 (auto), 0 (sequential), 1 (all rows) or k > 1 (k row groups per band)"); c.fwd_order = value; }
-    else if (!strcmp(name, "nt")) { JH_REQUIRE(value >= 0 && value <= 2, "nt must be 0 (temporal), 1 (nontemporal unless the working set is cache-resident) or 2 (always nontemporal)"); c.nt = value; }
-    else if (!strcmp(name, "nt_resident_mib")) { JH_REQUIRE(value >= 0, "nt_resident_mib must be >= 0"); c.nt_resident_mib = value; }
-    else if (!strcmp(name, "slab_cache")) { g_slab_cache_on.store(value ? 1 : 0); if (!value) jh_slab_trim(-1); }   // the switch is process-wide: so is the trim
-    else if (!strcmp(name, "bcast_item_fast")) { JH_REQUIRE(value >= -1 && value <= 1, "bcast_item_fast must be -1 (auto), 0 or 1"); c.bcast_item_fast = value; }
-    else if (!strcmp(name, "adj_split")) { JH_REQUIRE(value >= -1 && value <= 65535, "adj_split must be -1 (auto), 0 (never: ordered walk) or the number of row parts"); c.adj_split = value; }
-    else if (!strcmp(name, "adj_rows_per_launch")) { JH_REQUIRE(value >= 0, "adj_rows_per_launch must be >= 0"); c.adj_rows_per_launch = value; }
-    else if (!strcmp(name, "autotune")) { c.autotune = value ? 1 : 0; }
-    else if (!strcmp(name, "graphs")) { c.graphs = value ? 1 : 0; }
-    else if (!strcmp(name, "small_loop")) { c.small_loop = value ? 1 : 0; }
-    else if (!strcmp(name, "force_dist")) { c.force_dist = value ? 1 : 0; }
-    else if (!strcmp(name, "step_chain")) { JH_REQUIRE(value >= -1 && value <= 1, "step_chain must be -1 (auto), 0 or 1"); c.step_chain = value; }
-    else if (!strcmp(name, "step_chunk")) { JH_REQUIRE(value == 0 || value == 8 || value == 16 || value == 32, "step_chunk must be 0 (automatic), 8, 16 or 32"); c.step_chunk = value; }
-    else if (!strcmp(name, "step_band")) { JH_REQUIRE(value >= -1 && value < ((int64_t)1 << 24), "step_band must be -1 (default), 0 (none) or a number of tiles"); c.step_band = value; }
-    else if (!strcmp(name, "general_xcd")) { JH_REQUIRE(value >= 0 && value <= 2, "general_xcd must be 0 (never), 1 (automatic) or 2 (always)"); c.general_xcd = value; }
-    else if (!strcmp(name, "lsqr_graph")) { c.lsqr_graph = value < 0 ? 0 : (value > 2 ? 2 : value); }
-    else if (!strcmp(name, "grid_tile")) { JH_REQUIRE(value == 0 || value == 1 || value == 2 || value == 4 || value == 8, "grid_tile must be 0 (k_grid_diag), 1 (automatic) or 2 / 4 / 8 lines per workgroup"); c.grid_tile = value; }
-    else if (!strcmp(name, "dense_mixed")) { JH_REQUIRE(value == 0 || value == 1, "dense_mixed must be 0 or 1"); c.dense_mixed = value; }
-    else if (!strcmp(name, "general_tile")) { JH_REQUIRE(value == 0 || value == 1 || value == 2 || value == 4, "general_tile must be 0 (one-line kernels), 1 (automatic), 2 or 4 lines per workgroup"); c.general_tile = value; }
-    else if (!strcmp(name, "general_list")) { JH_REQUIRE(value >= 0 && value <= 3, "general_list must be 0 (never), 1 (automatic), 2 (always the four-line lists) or 3 (always the per-line lists)"); c.general_list = value; }
-    else if (!strcmp(name, "small_loop_max_kib")) { JH_REQUIRE(value >= 0, "small_loop_max_kib must be >= 0"); c.small_loop_max_kib = value; }
-    else if (!strcmp(name, "dense_list")) { JH_REQUIRE(value >= 0 && value <= 2, "dense_list must be 0 (the grid over every block pair), 1 (the children's lists) or 2 (... also for few big children)"); c.dense_list = value; }
-    else if (!strcmp(name, "dense_list_shared")) { JH_REQUIRE(value == 0 || value == 1, "dense_list_shared must be 0 or 1"); c.dense_list_shared = value; }
-    else if (!strcmp(name, "dense_combine")) { JH_REQUIRE(value == 0 || value == 1, "dense_combine must be 0 or 1"); c.dense_combine = value; }
-    else if (!strcmp(name, "dense_list_rl_min")) { JH_REQUIRE(value == 0 || (value >= 4 && value <= 8), "dense_list_rl_min must be 0 (default) or a shift 4 .. 8"); c.dense_list_rl_min = value; }
-    else if (!strcmp(name, "dense_list_cpw")) { JH_REQUIRE(value == 0 || value == 1 || value == 2 || value == 4, "dense_list_cpw must be 0 (by column length), 1, 2 or 4"); c.dense_list_cpw = value; }
-    else if (!strcmp(name, "dense_grid")) { c.dense_grid = value ? 1 : 0; }
-    else if (!strcmp(name, "dense_direct")) { c.dense_direct = value ? 1 : 0; }
-    else if (!strcmp(name, "dense_list_split")) { JH_REQUIRE(value == 0 || value == 1, "dense_list_split must be 0 (columns in order) or 1 (automatic lane layout)"); c.dense_list_split = value; }
-    else if (!strcmp(name, "dense_fused")) { JH_REQUIRE(value == 0 || value == 1, "dense_fused must be 0 or 1"); c.dense_fused = value; }
-    else if (!strcmp(name, "cgls_trace")) { c.cgls_trace = value ? 1 : 0; }
-    else if (!strcmp(name, "cg_dev")) { c.cg_dev = value < 0 ? 0 : (value > 2 ? 2 : value); }
-    else if (!strcmp(name, "walk_memory")) { c.walk_memory = value ? 1 : 0; }
-    else if (!strcmp(name, "slab_free_floor_mib")) { JH_REQUIRE(value >= 0, "slab_free_floor_mib must be >= 0"); g_slab_free_floor_mib.store(value); }
-    else if (!strcmp(name, "alloc_role")) { JH_REQUIRE(value >= 0 && value <= 2, "alloc_role must be 0 (none), 1 (an operator's output) or 2 (data written once, read from then on)"); c.alloc_role = value; }
-    else if (!strcmp(name, "dense_fwd_wgs")) { JH_REQUIRE(value >= 0 && value <= 65536, "dense_fwd_wgs must be 0 (automatic) .. 65536"); c.dense_fwd_wgs = value; }
-    else if (!strcmp(name, "dense_gw")) { JH_REQUIRE(value >= 0 && value <= 4096, "dense_gw must be 0 (automatic) or 1 .. 4096 children per wave"); c.dense_gw = value; }
-    else if (!strcmp(name, "sum_group")) { JH_REQUIRE(value == 4 || value == 8 || value == 16, "sum_group must be 4, 8 or 16 terms per forward launch"); c.sum_group = value; }
-    else if (!strcmp(name, "bcast_band")) { c.bcast_band = value < 0 ? 0 : value; }
-    else if (!strcmp(name, "general_band")) { JH_REQUIRE(value == 8 || value == 16 || value == 32 || value == 64, "general_band must be 8, 16, 32 or 64 tiles"); c.general_band = value; }
-    else if (!strcmp(name, "fwd_ctiles")) { c.fwd_ctiles = value < -1 ? -1 : value; }
-    else if (!strcmp(name, "sum_adj_group")) { c.sum_adj_group = value == 16 ? 16 : 8; }
-    else if (!strcmp(name, "grid_diag")) { JH_REQUIRE(value >= 0 && value <= 4, "grid_diag must be 0 (general kernels), 1, 2 or 4 (packs per lane)"); c.grid_diag = value; }
-    else if (!strcmp(name, "tall_f")) { JH_REQUIRE(value >= 0 && value <= 1, "tall_f must be 0 or 1"); c.tall_f = value; }
-    else if (!strcmp(name, "red_blocks_wave")) { c.red_blocks_wave = value ? 1 : 0; }
-    else if (!strcmp(name, "adj_bare_chain")) { c.adj_bare_chain = value ? 1 : 0; }
-    else if (!strcmp(name, "adj_thin_mixed")) { c.adj_thin_mixed = value ? 1 : 0; }
-    else if (!strcmp(name, "grid_normal")) { JH_REQUIRE(value >= 0 && value <= 2, "grid_normal must be 0, 1 or 2"); c.grid_normal = value; }
-    else if (!strcmp(name, "grid_chain")) { JH_REQUIRE(value == 0 || value == 1, "grid_chain must be 0 or 1"); c.grid_chain = value; }
-    else if (!strcmp(name, "grid_step")) { JH_REQUIRE(value == 0 || value == 1, "grid_step must be 0 or 1"); c.grid_step = value; }
-    else if (!strcmp(name, "grid_chain_step")) { JH_REQUIRE(value == 0 || value == 1, "grid_chain_step must be 0 or 1"); c.grid_chain_step = value; }
-    else if (!strcmp(name, "grid_range")) { JH_REQUIRE(value == 0 || value == 1, "grid_range must be 0 or 1"); c.grid_range = value; }
-    else if (!strcmp(name, "grid_chain_range")) { JH_REQUIRE(value == 0 || value == 1, "grid_chain_range must be 0 or 1"); c.grid_chain_range = value; }
-    else if (!strcmp(name, "fwd_anchor")) { JH_REQUIRE(value >= -1 && value <= 1, "fwd_anchor must be -1 (rows of >= 64 KiB that are not whole packs), 0 (never) or 1 (always)"); c.fwd_anchor = value; }
-    else if (!strcmp(name, "ua_nt")) { JH_REQUIRE(value >= -1 && value <= 1, "ua_nt must be -1 (temporal accesses on rows off the 16-byte grid), 0 (temporal always) or 1 (nontemporal always)"); c.ua_nt = value; }
-    else if (!strcmp(name, "tall_unaligned")) { JH_REQUIRE(value >= 0 && value <= 1, "tall_unaligned must be 0 (general kernels) or 1 (under-aligned tall kernels)"); c.tall_unaligned = value; }
-    else if (!strcmp(name, "wide_twin")) { JH_REQUIRE(value >= 0 && value <= 2, "wide_twin must be 0 (never), 1 (automatic) or 2 (always)"); c.wide_twin = value; }
-    else if (!strcmp(name, "red_wgs")) { JH_REQUIRE(value >= 1 && value <= 1 << 20, "red_wgs out of range"); c.red_wgs = value; }
-    else return jh_fail(JH_ERR_INVALID, "jh_tune_set: unknown knob '%s'", name);
-    return JH_OK;
+    // the context's knobs, one row of jh_knobs.def each: a failed check stores nothing; the counters are read-only and have no branch here
+#define JH_KNOB(knob, dflt, check, msg) if (!strcmp(name, #knob)) { JH_REQUIRE(check, msg); c.knob = value; return JH_OK; }
+#define JH_KNOB_MAP(knob, dflt, stored) if (!strcmp(name, #knob)) { c.knob = stored; return JH_OK; }
+#define JH_COUNTER(knob, dflt)
+#include "jh_knobs.def"
+    // process-wide, not fields of a context
+    if (!strcmp(name, "slab_cache")) { g_slab_cache_on.store(value ? 1 : 0); if (!value) jh_slab_trim(-1); return JH_OK; }   // the switch is process-wide: so is the trim
+    if (!strcmp(name, "slab_free_floor_mib")) { JH_REQUIRE(value >= 0, "slab_free_floor_mib must be >= 0"); g_slab_free_floor_mib.store(value); return JH_OK; }
+    return jh_fail(JH_ERR_INVALID, "jh_tune_set: unknown knob '%s'", name);
 }
 
 int jh_tune_get(const char *name, int64_t *value)
 {
     JH_REQUIRE(name && value, "jh_tune_get: null argument");
     jh_context &c = jh_ctx();
-    if (!strcmp(name, "fwd_group")) *value = c.fwd_group;
-    else if (!strcmp(name, "fwd_unroll")) *value = c.fwd_unroll;
-    else if (!strcmp(name, "fwd_wg")) *value = c.fwd_wg;
-    else if (!strcmp(name, "adj_unroll")) *value = c.adj_unroll;
-    else if (!strcmp(name, "adj_depth")) *value = c.adj_depth;
-    else if (!strcmp(name, "adj_wg")) *value = c.adj_wg;
-    else if (!strcmp(name, "fwd_order")) *value = c.fwd_order;
-    else if (!strcmp(name, "nt")) *value = c.nt;
-    else if (!strcmp(name, "nt_resident_mib")) *value = c.nt_resident_mib;
-    else if (!strcmp(name, "slab_cache")) *value = g_slab_cache_on.load();
-    else if (!strcmp(name, "slab_cached_mib")) *value = (int64_t)(jh_slab_cached_bytes(c.device) >> 20);
-    else if (!strcmp(name, "bcast_item_fast")) *value = c.bcast_item_fast;
-    else if (!strcmp(name, "adj_split")) *value = c.adj_split;
-    else if (!strcmp(name, "last_adj_parts")) *value = c.last_adj_parts;
-    else if (!strcmp(name, "adj_rows_per_launch")) *value = c.adj_rows_per_launch;
-    else if (!strcmp(name, "autotune")) *value = c.autotune;
-    else if (!strcmp(name, "graphs")) *value = c.graphs;
-    else if (!strcmp(name, "small_loop")) *value = c.small_loop;
-    else if (!strcmp(name, "force_dist")) *value = c.force_dist;
-    else if (!strcmp(name, "step_chain")) *value = c.step_chain;
-    else if (!strcmp(name, "step_band")) *value = c.step_band;
-    else if (!strcmp(name, "step_chunk")) *value = c.step_chunk;
-    else if (!strcmp(name, "last_step_chain")) *value = c.last_step_chain;
-    else if (!strcmp(name, "general_xcd")) *value = c.general_xcd;
-    else if (!strcmp(name, "graph_replays")) *value = c.graph_replays;
-    else if (!strcmp(name, "last_fwd_rows_per_wg")) *value = c.last_fwd_rows_per_wg;
-    else if (!strcmp(name, "last_adj_launches")) *value = c.last_adj_launches;
-    else if (!strcmp(name, "lsqr_graph")) *value = c.lsqr_graph;
-    else if (!strcmp(name, "last_lsqr_graph")) *value = c.last_lsqr_graph;
-    else if (!strcmp(name, "grid_diag")) *value = c.grid_diag;
-    else if (!strcmp(name, "grid_tile")) *value = c.grid_tile;
-    else if (!strcmp(name, "sum_group")) *value = c.sum_group;
-    else if (!strcmp(name, "bcast_band")) *value = c.bcast_band;
-    else if (!strcmp(name, "general_band")) *value = c.general_band;
-    else if (!strcmp(name, "fwd_ctiles")) *value = c.fwd_ctiles;
-    else if (!strcmp(name, "sum_adj_group")) *value = c.sum_adj_group;
-    else if (!strcmp(name, "general_tile")) *value = c.general_tile;
-    else if (!strcmp(name, "general_list")) *value = c.general_list;
-    else if (!strcmp(name, "dense_list")) *value = c.dense_list;
-    else if (!strcmp(name, "small_loop_max_kib")) *value = c.small_loop_max_kib;
-    else if (!strcmp(name, "dense_list_split")) *value = c.dense_list_split;
-    else if (!strcmp(name, "dense_direct")) *value = c.dense_direct;
-    else if (!strcmp(name, "dense_grid")) *value = c.dense_grid;
-    else if (!strcmp(name, "dense_list_shared")) *value = c.dense_list_shared;
-    else if (!strcmp(name, "dense_combine")) *value = c.dense_combine;
-    else if (!strcmp(name, "dense_list_rl_min")) *value = c.dense_list_rl_min;
-    else if (!strcmp(name, "dense_list_cpw")) *value = c.dense_list_cpw;
-    else if (!strcmp(name, "last_dense_rl")) *value = c.last_dense_rl;
-    else if (!strcmp(name, "last_general_list")) *value = c.last_general_list;
-    else if (!strcmp(name, "dense_mixed")) *value = c.dense_mixed;
-    else if (!strcmp(name, "dense_fused")) *value = c.dense_fused;
-    else if (!strcmp(name, "cgls_trace")) *value = c.cgls_trace;
-    else if (!strcmp(name, "cg_dev")) *value = c.cg_dev;
-    else if (!strcmp(name, "walk_memory")) *value = c.walk_memory;
-    else if (!strcmp(name, "alloc_role")) *value = c.alloc_role;
-    else if (!strcmp(name, "slab_free_floor_mib")) *value = g_slab_free_floor_mib.load();
-    else if (!strcmp(name, "slab_probed")) *value = jh_slab_probed(c.device);
-    else if (!strcmp(name, "last_alloc_choice")) *value = jh_slab_last_choice();
-    else if (!strcmp(name, "last_cg_graph")) *value = c.last_cg_graph;
-    else if (!strcmp(name, "last_cgls_overlaps")) *value = c.last_cgls_overlaps;
-    else if (!strcmp(name, "dense_gw")) *value = c.dense_gw;
-    else if (!strcmp(name, "dense_fwd_wgs")) *value = c.dense_fwd_wgs;
-    else if (!strcmp(name, "last_dense_fused")) *value = c.last_dense_fused;
-    else if (!strcmp(name, "last_launches")) *value = c.last_launches;
-    else if (!strcmp(name, "tall_unaligned")) *value = c.tall_unaligned;
-    else if (!strcmp(name, "red_blocks_wave")) *value = c.red_blocks_wave;
-    else if (!strcmp(name, "adj_bare_chain")) *value = c.adj_bare_chain;
-    else if (!strcmp(name, "adj_thin_mixed")) *value = c.adj_thin_mixed;
-    else if (!strcmp(name, "grid_normal")) *value = c.grid_normal;
-    else if (!strcmp(name, "grid_chain")) *value = c.grid_chain;
-    else if (!strcmp(name, "last_grid_chain_shape")) *value = c.last_grid_chain_shape;
-    else if (!strcmp(name, "grid_step")) *value = c.grid_step;
-    else if (!strcmp(name, "last_grid_step_shape")) *value = c.last_grid_step_shape;
-    else if (!strcmp(name, "grid_chain_step")) *value = c.grid_chain_step;
-    else if (!strcmp(name, "last_grid_chain_step_shape")) *value = c.last_grid_chain_step_shape;
-    else if (!strcmp(name, "grid_range")) *value = c.grid_range;
-    else if (!strcmp(name, "last_grid_range_shape")) *value = c.last_grid_range_shape;
-    else if (!strcmp(name, "grid_chain_range")) *value = c.grid_chain_range;
-    else if (!strcmp(name, "last_grid_chain_range_shape")) *value = c.last_grid_chain_range_shape;
-    else if (!strcmp(name, "fwd_anchor")) *value = c.fwd_anchor;
-    else if (!strcmp(name, "ua_nt")) *value = c.ua_nt;
-    else if (!strcmp(name, "tall_f")) *value = c.tall_f;
-    else if (!strcmp(name, "wide_twin")) *value = c.wide_twin;
-    else if (!strcmp(name, "red_wgs")) *value = c.red_wgs;
-    else if (!strcmp(name, "last_fwd_walk")) *value = c.last_fwd_walk;
-    else return jh_fail(JH_ERR_INVALID, "jh_tune_get: unknown knob '%s'", name);
-    return JH_OK;
+    // every row of jh_knobs.def, knob or counter, reads its field
+#define JH_GET(knob) if (!strcmp(name, #knob)) { *value = c.knob; return JH_OK; }
+#define JH_KNOB(knob, dflt, check, msg) JH_GET(knob)
+#define JH_KNOB_MAP(knob, dflt, stored) JH_GET(knob)
+#define JH_COUNTER(knob, dflt) JH_GET(knob)
+#include "jh_knobs.def"
+#undef JH_GET
+    // process-wide or computed, not fields of a context
+    if (!strcmp(name, "slab_cache")) { *value = g_slab_cache_on.load(); return JH_OK; }
+    if (!strcmp(name, "slab_free_floor_mib")) { *value = g_slab_free_floor_mib.load(); return JH_OK; }
+    if (!strcmp(name, "slab_cached_mib")) { *value = (int64_t)(jh_slab_cached_bytes(c.device) >> 20); return JH_OK; }
+    if (!strcmp(name, "slab_probed")) { *value = jh_slab_probed(c.device); return JH_OK; }
+    if (!strcmp(name, "last_alloc_choice")) { *value = jh_slab_last_choice(); return JH_OK; }
+    return jh_fail(JH_ERR_INVALID, "jh_tune_get: unknown knob '%s'", name);
 }
 
 }  // extern "C"

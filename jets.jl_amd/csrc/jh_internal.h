@@ -75,96 +75,17 @@ struct jh_context {
     size_t scratch_cap = 0;
     unsigned *chain_sync = nullptr;    // chained one-pass step (k_tall_diag_bidiag_chain): [0] ticket counter, [1] unused, [2..] per-tile hand-off flags
     int64_t chain_sync_cap = 0;
-    int64_t step_chain = -1;           // knob: one-pass step as chained row chunks: -1 automatic, 0 never, 1 always (when the shape allows)
-    // tuning knobs (jh_tune_set)
-    // 0 = pick from the problem size (jh_tall.hip: pick_fwd_shape / pick_adj_shape)
-    int64_t fwd_group = 0;             // block rows streamed per workgroup (tall forward)
-    int64_t fwd_unroll = 0;            // 16-byte vectors per thread per block (tall forward)
-    int64_t fwd_wg = 0;                // threads per workgroup (tall forward)
-    int64_t adj_unroll = 0;            // 16-byte vectors per thread (tall adjoint / fused normal)
-    int64_t adj_depth = 0;             // block rows in flight per thread (tall adjoint / fused normal)
-    int64_t adj_wg = 0;                // threads per workgroup (tall adjoint / fused normal)
-    int64_t fwd_order = -1;            // -1: automatic; 0: sequential row sweep; 1: all row groups concurrent; k>1: bands of k row groups
-    int64_t adj_rows_per_launch = 0;   // tall adjoint / fused normal: block rows per launch (0 = all rows in one launch); same bits either way
-    int64_t adj_split = -1;            // split-row walk of the adjoint-shaped kernels: -1 automatic, 0 never (ordered, bit-exact), k > 1 parts
-    int64_t last_adj_parts = 1;        // row parts of the most recent tall adjoint / fused normal / one-pass step (read-only knob)
-    int64_t bcast_item_fast = -1;      // batched broadcasts with a shared operand: items as the fastest block index (-1 automatic, 0 never, 1 always)
-    int64_t nt = 1;                    // nontemporal loads/stores on the streamed operands: 0 never, 1 unless the working set stays in the Infinity Cache (jh_stream_nt), 2 always
-    int64_t nt_resident_mib = 256;     // knob: working sets up to this many MiB count as cache-resident for nt = 1 (0: none -- everything streams).  256 from
-                                       // profiles/exp_r05_nt_small.txt: with coefficients + range vector <= 256 MiB temporal loads win (pair +7 %, one-pass step +7 ... +19 %,
-                                       // LSQR iteration -9 %), from 512 MiB on nontemporal ones do (+10 ... +15 %)
-    int64_t autotune = 1;              // time both grid walks of the tall forward once per large operator
-    int64_t general_xcd = 1;           // general M x K kernels: 1 = XCD-aware (line, tile) decode from 32 MiB of input on, else line by line; 0 never; 2 always
-    int64_t graphs = 1;                // replay launch-bound per-block loops as hipGraphs (jh_blockop.hip: run_loop_graphed)
-    int64_t force_dist = 0;            // tests: jh_lsqr_solve_partitioned runs its exchange even with ONE rank (validates the pipelined path on a one-GPU box)
-    int64_t small_loop = 1;            // operators mixing small DENSE children with other kinds: the whole block loop in one launch (0: the per-block loop)
-    int64_t graph_replays = 0;         // read-only counter: hipGraphLaunch calls made by run_loop_graphed
     uint64_t buf_gen = 0;              // bumped whenever part_dev / scratch_dev is reallocated: captured graphs holding the old pointers are stale
-    int64_t red_wgs = 16384;           // workgroups of a reduction launch (4 packs per lane in flight); profiles/sweep_r01_reduce.txt
-    int64_t last_fwd_rows_per_wg = 0;  // block rows per workgroup of the most recent tall forward launch (read-only knob)
-    int64_t last_adj_launches = 1;     // kernel launches of the most recent tall adjoint / fused normal call (read-only knob)
-    int64_t last_fwd_walk = 0;         // grid walk used by the most recent tall forward launch (read-only knob)
-    int64_t last_step_chain = 0;       // row chunks of the most recent one-pass step (0: the plain walk) (read-only knob)
-    int64_t step_chunk = 0;            // knob: rows per chunk of the chained one-pass step: 0 automatic (32 rows x 256 lanes for all-diagonal operators, else 8), 8, 16, 32
-    int64_t step_band = -1;            // knob: the chained one-pass step in column bands of this many tiles (-1: the default, 0: none -- tiles fastest over the whole row)
-    int64_t grid_diag = 1;             // knob: M x K grids of plain diagonals on the branch-free kernel (0: the general kernels)
-    int64_t grid_tile = 1;             // knob: ... register-tiled (k_grid_tile: R lines x one tile per workgroup): 1 automatic R, 2 / 4 / 8 that R, 0: k_grid_diag
-    int64_t general_tile = 1;          // knob: grids of EQUAL elementwise blocks of any kinds register-tiled (k_general_tile: two lines x one tile per workgroup); 0: k_block_*_general_vec
-    int64_t general_list = 1;          // knob: sparse grids walk lists of their non-zero steps (k_general_tile LIST): 1 automatic (jh_general.hip: launch_general_tile), 0 never, 2 always the four-line lists, 3 always the per-line lists
-    int64_t last_general_list = 0;     // read-only: the most recent register-tiled general launch walked 0 no list, 1 its four-line lists, 2 its per-line lists
-    int64_t sum_group = 16;            // knob: terms of a fused JetSum per FORWARD launch (16; 8 / 4 = round 3's / round 2's grouping, for A/B); the adjoint takes 8 (4)
-    int64_t bcast_band = 0;            // knob: batched broadcasts with a shared operand in column bands of this many tiles (0: 32; 1: items fastest, no bands)
-    int64_t general_band = 8;          // knob: tiles of every line the general M x K kernels walk before the next group of tiles starts: 8, 16, 32, 64
-    int64_t fwd_ctiles = -1;           // knob: tall forward in column bands of this many tiles (-1: the shape's own, 0: none)
-    int64_t sum_adj_group = 16;        // knob: terms of a fused JetSum ADJOINT per launch (each keeps its own accumulator): 16 (one row in flight; +1-2 % at 11-16 terms), or 8
-    int64_t small_loop_max_kib = 512;  // knob: operators of small dense children whose matrices together reach this many KiB take the batched route (lists) instead of the one-launch loop
-    int64_t dense_list = 1;            // knob: the dense children of dense_mixed operators from their LIST (k_gemv_*_list, late round 5); 0: the grid over every block pair (k_gemv_*_mixed)
-    int64_t dense_list_split = 1;      // knob: ... 1 the rows pass picks its lane layout (column groups per workgroup: deterministic, tolerance parity), 0 columns in order (the sequential loop's bits)
-    int64_t dense_grid = 0;            // knob, read by jh_blockop_create: M x K grids of uniform dense children on the list route (0; late round 5: 8 x 8 of 1024^2 1.8 -> 5.5 TB/s forward, 32 x 32 of 256^2 0.43 -> 4.6) or as one tall batch per block column (1: rounds 2-4)
-    int64_t dense_direct = 1;          // knob: block-diagonal operators of dense children in ONE launch (the list kernels write the output vector); 0: scratch + combine
-    int64_t dense_list_shared = 1;     // knob: the rows pass over children with columns off the 16-byte grid numbers its workgroups XCD by XCD and loads temporal (k_gemv_rows_list<SHARED>); 0: round 5's streaming loads
-    int64_t dense_combine = 1;         // knob: operators whose non-zero blocks are all dense children combine the products from per-line lists (k_combine_dense, round 6); 0: the general kernel's table walk
-    int64_t dense_list_rl_min = 0;     // knob: lists of dense children whose columns start off the 16-byte grid keep at least 2^this row lanes per workgroup in the rows pass (0: 6 = 1 KiB runs per column; 4 = round 5's rule)
-    int64_t dense_list_cpw = 0;        // knob: columns per lane group of the list kernel of y = B' x: 0 by column length, 1 / 2 / 4
-    int64_t last_dense_rl = 0;         // read-only: row lanes per workgroup of the latest rows pass of the list kernels (256: columns in order)
-    int64_t dense_mixed = 1;           // knob: operators mixing big dense children with other kinds: one batched launch + one combine launch (0: the per-block loop)
-    int64_t last_launches = 0;         // read-only: kernel launches of the most recent dense_mixed forward / adjoint
-    int64_t dense_fused = 1;           // knob: tall / wide adjoint of many small uniform dense children on the fused kernel (k_gemv_cols_fused, round 4); 0: the three-launch path
-    int64_t dense_fwd_wgs = 0;         // knob: workgroups the batched dense forward splits its columns for (0 = 2048)
-    int64_t dense_gw = 0;              // knob: children per WAVE of that kernel (0 = from the operator's shape)
-    int64_t last_dense_fused = 0;      // read-only: 1 when the most recent batched dense adjoint ran on the fused kernel
     double adj_in_scale = 1.0;         // internal: the MIXED tall adjoint multiplies every d_i by it first (jh_blockop_mul_adj_scaled on rows of several kinds); 1 outside that call
-    int64_t tall_f = 1;                // knob: F(m) of a tall nonlinear operator of elementwise children on the tall tiling (jh_blockop_f): 1 yes, 0 the general kernels
-    int64_t ua_nt = -1;                // knob: accesses of the tall kernels on rows off the 16-byte grid: -1 temporal there, nontemporal on aligned rows; 0 / 1 temporal / nontemporal always
-    int64_t tall_unaligned = 1;        // knob: tall operators whose rows are not whole, 16-byte aligned packs (odd block lengths in one slab) on the under-aligned tall kernels (jh_tall.hip: tall_unaligned_ok); 0: the general kernels as before
-    int64_t red_blocks_wave = 1;       // knob: per-block reductions of many short blocks with a wave per block (k_reduce_blocks_wave); 0: a workgroup per block
-    int64_t adj_bare_chain = 1;        // knob: jh_blockop_mul_adj / _normal_mul of tall operators with rows of several kinds / off the 16-byte grid on the chain kernels (rows up to 4 MiB); 0: k_tall_diag_adj<MIXED>
-    int64_t adj_thin_mixed = 1;        // knob: the MIXED tall adjoint on thin workgroups when the fat shape would not fill the chip (rows of 1-8 MiB); 0: round 5's rule
-    int64_t grid_normal = 1;           // knob: (A', A) on an N x (2 .. 4) grid of equal elementwise blocks in one pass (jh_grid_normal.hip); 2: grids of plain diagonals only; 0: JH_ERR_UNSUPPORTED as in rounds 1-5 (the caller chains the two stages)
-    int64_t grid_chain = 1;            // knob: jh_chain_create on an N x (2 .. 4) grid of equal elementwise blocks (jh_grid_chain.hip): 1 yes, 0 JH_ERR_UNSUPPORTED as before (the caller runs the chain stage by stage)
-    int64_t last_grid_chain_shape = 0; // how the most recent grid chain was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts, bit 2 the stages after A' on the folded parts
-    int64_t grid_step = 1;             // knob: jh_blockop_bidiag_step (and the LSQR / CGLS loops of jh_lsqr_solve / jh_cgls_solve) on an N x (2 .. 4) grid of equal elementwise blocks in one pass (jh_grid_step.hip): 1 yes, 0 JH_ERR_UNSUPPORTED as before
-    int64_t last_grid_step_shape = 0;  // how the most recent grid step was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
-    int64_t grid_chain_step = 0;       // knob: jh_chain_bidiag_step (and the LSQR / CGLS loops of jh_lsqr_solve_chain / jh_cgls_solve_chain) on a FORWARD chain through an N x (2 .. 4) grid in one pass (jh_grid_chain_step.hip): 1 yes, 0 (default) JH_ERR_UNSUPPORTED as before
-    int64_t last_grid_chain_step_shape = 0;   // how the most recent grid chain step was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
-    int64_t grid_range = 0;            // knob: jh_blockop_mul_adj_range / _normal_mul_range / _bidiag_step_range on an N x (2 .. 4) grid of equal elementwise blocks, the range being positions INSIDE a block (jh_grid_range.hip): 1 yes, 0 (default) JH_ERR_UNSUPPORTED as before
-    int64_t grid_chain_range = 0;      // knob: jh_chain_apply_range (ADJOINT / NORMAL) and jh_chain_bidiag_step_range (with grid_chain_step = 1 as well) on a chain through an N x (2 .. 4) grid, the range being positions INSIDE a block: 1 yes, 0 (default) JH_ERR_UNSUPPORTED as before
-    int64_t last_grid_chain_range_shape = 0;   // how the most recent ranged grid-chain call was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
-    int64_t last_grid_range_shape = 0; // how the most recent ranged grid call was launched (read-only knob): bit 0 nontemporal loads, bit 1 rows in parts
-    int64_t fwd_anchor = -1;           // knob: the tall forward of rows that are not whole packs on lanes anchored to each row's own 16-byte grid (k_tall_fwd_anchored): -1 from 64 KiB rows on, 0 never, 1 always
-    int64_t wide_twin = 1;             // knob: wide elementwise operators on their tall twin: 0 never (general kernels), 1 adjoint always + forward from 16 MiB blocks, 2 both always (tests)
     const double *step_coef_dev = nullptr;   // internal, set around the calls of the graph-captured LSQR loop: the one-pass step reads (alpha, beta) from
     const int *step_done_dev = nullptr;      // here instead of its arguments and returns at once when *step_done_dev != 0 (jh_lsqr.hip: lsqr_graph_impl)
     int step_skip_fold = 0;                  // internal: ... and leaves the fold of its per-workgroup partial sums (part_dev[0 .. last_step_parts)) to the caller
     int64_t last_step_parts = 0;             // per-workgroup partial sums the most recent one-pass step wrote
-    int64_t lsqr_graph = 1;            // knob: small operators' LSQR loop with device-resident recurrences, replayed as a hipGraph (0: the host loop)
-    int64_t last_lsqr_graph = 0;       // read-only: graph replays of the most recent jh_lsqr_solve (0: the host loop ran)
-    int64_t walk_memory = 1;           // knob: a new tall operator starts with the forward walk the last operator of its shape chose (0: every operator measures)
-    int64_t alloc_role = 0;            // knob: what the NEXT vectors of this context are for -- 0 unknown, 1 an operator's output (the cached slab that is fastest to write), 2 data written once and read from then on (the slowest to write: those read fastest); slabs >= 4 GiB only
-    int64_t cg_dev = 1;                // knob: small operators' CGLS / CG-on-the-normal-equations loops on the fused kernels of cg_dev_impl (graph-replayed unless lsqr_graph = 0); 0: cgls_impl / cgnr_impl
-    int64_t last_cg_graph = 0;         // read-only: graph replays of the most recent jh_cgls_solve / jh_cgnr_solve (0: a host-driven loop ran)
-    int64_t cgls_trace = 0;            // knob (tests): jh_cgls_solve_team stamps every member's pass 1 of its first iteration with events ...
-    int64_t last_cgls_overlaps = -1;   // read-only: ... and counts the consecutive members whose pass 1 began before the previous member's had finished (-1: not traced)
+    // tuning knobs (jh_tune_set) and read-only counters (jh_tune_get): one int64_t field per row of jh_knobs.def, with the row's default
+#define JH_KNOB(name, dflt, check, msg) int64_t name = dflt;
+#define JH_KNOB_MAP(name, dflt, stored) int64_t name = dflt;
+#define JH_COUNTER(name, dflt) int64_t name = dflt;
+#include "jh_knobs.def"
     int red_defer = 0;                 // internal, set around ONE reduction: enqueue it and its read-back, do not wait (jh_dot_begin / jh_dot_end)
     int adj_from_found = 0;            // internal, set around ONE call: the tall adjoint continues from what its output holds (the
                                        // forward of a wide operator through its tall twin: `_d .+=` into d as found, src/Jets.jl:1024); never split

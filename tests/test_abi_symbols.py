@@ -107,16 +107,19 @@ def test_every_entry_point_is_mapped_to_the_reference_in_integration_md():
 
 
 def test_every_knob_the_library_accepts_is_described_in_the_header():
-    """jh_tune_set / jh_tune_get / jh_blockop_tune_* take a NAME: the names the sources compare against are the interface, so each one
+    """jh_tune_set / jh_tune_get / jh_blockop_tune_* take a NAME: the names the sources know are the interface, so each one
     must appear, quoted, in include/jetship.h's description of the knobs."""
     import re
 
+    from . import knob_table
+
     hdr = open(os.path.join(ROOT, "include", "jetship.h")).read()
-    names = set()
+    names = set(knob_table.rows())                                              # the context's knobs and counters: the rows of jh_knobs.def
     import glob
 
-    for f in glob.glob(os.path.join(ROOT, "jets.jl_amd", "csrc", "*.hip")):     # (jh_core.hip: the context's knobs; jh_tall.hip: the per-operator ones)
+    for f in glob.glob(os.path.join(ROOT, "jets.jl_amd", "csrc", "*.hip")):     # (jh_core.hip: the five process-wide names; jh_tall.hip: the per-operator ones)
         names |= set(re.findall(r'strcmp\(name, "([a-z_0-9]+)"\)', open(f).read()))
+    assert set(knob_table.PROCESS_WIDE_SETTABLE + knob_table.PROCESS_WIDE_READ_ONLY) <= names
     assert len(names) > 40
     missing = sorted(n for n in names if f'"{n}"' not in hdr)
     assert not missing, f"knobs without a description in include/jetship.h: {missing}"

@@ -3,6 +3,8 @@ next to both calls and its counter; the library's default is 0; and the row part
 import os
 import re
 
+from . import knob_table
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -30,11 +32,11 @@ def test_header_describes_the_knob_the_counter_and_the_range_of_a_grid_chain():
 
 
 def test_the_default_is_zero_and_the_counter_is_read_only():
-    assert re.search(r"int64_t grid_chain_range = 0;", _read("jets.jl_amd", "csrc", "jh_internal.h"))
-    core = _read("jets.jl_amd", "csrc", "jh_core.hip")
-    assert core.count('strcmp(name, "grid_chain_range")') == 2                  # set and get
-    assert core.count('strcmp(name, "last_grid_chain_range_shape")') == 1       # get only
-    assert '"grid_chain_range must be 0 or 1"' in core
+    table = knob_table.rows()                                                   # jh_knobs.def: the field, jh_tune_set and jh_tune_get come from the row
+    knob = table["grid_chain_range"]
+    assert knob.kind == "JH_KNOB" and knob.default == 0                         # set and get
+    assert table["last_grid_chain_range_shape"].kind == "JH_COUNTER"            # get only
+    assert knob.rule == "value == 0 || value == 1" and knob.message == "grid_chain_range must be 0 or 1"
     abi = _read("jets.jl_amd", "csrc", "jh_tall_chain.hip")
     assert "a grid chain has no ranged form (apply the whole vector)" in abi     # the refusals of knob 0, word for word
     assert "a grid chain has no one-pass step (run the FORWARD chain, then the ADJOINT)" in abi

@@ -7,6 +7,8 @@ import sys
 
 import pytest
 
+from . import knob_table
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "jets.jl_amd", "libjetship.so")
 
@@ -27,9 +29,9 @@ def test_header_documents_the_knob_and_the_counter():
 
 
 def test_the_library_accepts_the_knob_with_default_zero():
-    core = _read("jets.jl_amd", "csrc", "jh_core.hip")
-    assert core.count('strcmp(name, "grid_chain_step")') == 2 and 'strcmp(name, "last_grid_chain_step_shape")' in core   # set and get; the counter is read-only
-    assert re.search(r"int64_t grid_chain_step = 0;", _read("jets.jl_amd", "csrc", "jh_internal.h"))
+    table = knob_table.rows()                                                   # jh_knobs.def: the field, jh_tune_set and jh_tune_get come from the row
+    assert table["grid_chain_step"].kind == "JH_KNOB" and table["last_grid_chain_step_shape"].kind == "JH_COUNTER"   # set and get; the counter is read-only
+    assert table["grid_chain_step"].default == 0
     assert "jh_grid_chain_step.hip" in _read("jets.jl_amd", "csrc", "Makefile")
 
 

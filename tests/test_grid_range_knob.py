@@ -1,7 +1,8 @@
 """CPU checks of the knob grid_range (the ranged calls on N x K grids, jh_grid_range.hip): the header describes it, its counter and the grid
 meaning of the range next to the three calls, and the library's default is 0."""
 import os
-import re
+
+from . import knob_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -29,11 +30,11 @@ def test_header_describes_the_knob_the_counter_and_the_range_of_a_grid():
 
 
 def test_the_default_is_zero_and_the_counter_is_read_only():
-    assert re.search(r"int64_t grid_range = 0;", _read("jets.jl_amd", "csrc", "jh_internal.h"))
-    core = _read("jets.jl_amd", "csrc", "jh_core.hip")
-    assert core.count('strcmp(name, "grid_range")') == 2                        # set and get
-    assert core.count('strcmp(name, "last_grid_range_shape")') == 1             # get only
-    assert '"grid_range must be 0 or 1"' in core
+    table = knob_table.rows()                                                   # jh_knobs.def: the field, jh_tune_set and jh_tune_get come from the row
+    knob = table["grid_range"]
+    assert knob.kind == "JH_KNOB" and knob.default == 0                         # set and get
+    assert table["last_grid_range_shape"].kind == "JH_COUNTER"                  # get only
+    assert knob.rule == "value == 0 || value == 1" and knob.message == "grid_range must be 0 or 1"
     assert "jh_grid_range.hip" in _read("jets.jl_amd", "csrc", "Makefile")
 
 
