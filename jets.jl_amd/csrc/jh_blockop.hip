@@ -579,7 +579,6 @@ int jh_blockop_f(const jh_blockop *op, jh_bvec *d, const jh_bvec *m)
     if (use_dense_mixed(op)) return dense_mixed(op, d->data, m->data, false, true);
     if (!op->elementwise) return run_loop_graphed(op, 2, d->data, m->data, [&] { return loop_fwd(op, d->data, m->data, true); });
     return jhb::general_fwd(op, d->data, m->data, 1);
-    return jh_fail(JH_ERR_INVALID, "jh_blockop_f: unknown dtype %d", op->dtype);
 }
 
 int jh_blockop_mul(const jh_blockop *op, jh_bvec *d, const jh_bvec *m)
@@ -614,7 +613,6 @@ int jh_blockop_mul(const jh_blockop *op, jh_bvec *d, const jh_bvec *m)
         return st;
     }
     return jhb::general_fwd(op, d->data, m->data);
-    return jh_fail(JH_ERR_INVALID, "jh_blockop_mul: unknown dtype %d", op->dtype);
 }
 
 int jh_blockop_mul_adj(const jh_blockop *op, jh_bvec *m, const jh_bvec *d)
@@ -641,7 +639,6 @@ int jh_blockop_mul_adj(const jh_blockop *op, jh_bvec *m, const jh_bvec *d)
         (tall_fast_ok(op->twin, m->data, d->data) || tall_mixed_ok(op->twin, m->data, d->data) || tall_unaligned_ok(op->twin, m->data, d->data)))
         return jh_blockop_mul(op->twin, m, d);
     return jhb::general_adj(op, m->data, d->data);
-    return jh_fail(JH_ERR_INVALID, "jh_blockop_mul_adj: unknown dtype %d", op->dtype);
 }
 
 int jh_blockop_mul_adj_range(const jh_blockop *op, jh_bvec *m, const jh_bvec *d, int64_t first_elem, int64_t count)
@@ -668,7 +665,6 @@ int jh_blockop_mul_adj_range(const jh_blockop *op, jh_bvec *m, const jh_bvec *d,
                "jh_blockop_mul_adj_range: chunk boundaries must be 16-byte aligned (the last chunk may end with the vector)");
     if (mixed) return jhb::tall_adj(op, m->data, d->data, 0, true, first_elem, first_elem + count);
     return jhb::tall_adj(op, m->data, d->data, 0, false, first_elem, first_elem + count);
-    return jh_fail(JH_ERR_INVALID, "jh_blockop_mul_adj_range: unknown dtype %d", op->dtype);
 }
 
 int jh_blockop_normal_mul(const jh_blockop *op, jh_bvec *y, const jh_bvec *m)
@@ -691,7 +687,6 @@ int jh_blockop_normal_mul(const jh_blockop *op, jh_bvec *y, const jh_bvec *m)
                        "jh_blockop_normal_mul: fused A'A needs a tall (>= 2 rows) operator of equal elementwise rows or an N x (2 .. 4) grid of equal "
                        "diagonals; chain jh_blockop_mul and jh_blockop_mul_adj instead");
     return jhb::tall_adj(op, y->data, m->data, 1, false);
-    return jh_fail(JH_ERR_INVALID, "jh_blockop_normal_mul: unknown dtype %d", op->dtype);
 }
 
 // The fused A'A over the elements [first_elem, first_elem + count) of the domain: for a host that pipelines the exchange of y range by
@@ -727,7 +722,6 @@ int jh_blockop_normal_mul_range(const jh_blockop *op, jh_bvec *y, const jh_bvec 
         return jh_fail(JH_ERR_UNSUPPORTED,
                        "jh_blockop_normal_mul_range: fused A'A needs a tall (>= 2 rows) operator of equal elementwise rows");
     return jhb::tall_adj(op, y->data, m->data, 1, false, lo, hi);
-    return jh_fail(JH_ERR_INVALID, "jh_blockop_normal_mul_range: unknown dtype %d", op->dtype);
 }
 
 

@@ -153,6 +153,16 @@ template <typename S, int NS, typename V> __device__ inline double vnorm2_from(V
 }  // namespace
 
 struct TallShape { int wg, unroll, aux, order, ctiles = 0; };   // aux = rows per workgroup (forward) / rows in flight (adjoint); ctiles: forward column bands (tiles per band, 0: none)
+// where the tall kernels find the diagonals of an all-DIAG operator: row i at base + i * stride scalars when they are blocks of one slab (diag_strided), else
+// base == nullptr and every row's pointer comes from the device block table
+// A launcher's choice of kernel as a VALUE: the address of the instantiation and the compile-time constants of the table row it came from (workgroup size,
+// packs per lane, rows in flight / rows per chunk, as far as the kernel has them); k == nullptr: no row matched.  The launcher sizes its grid from these.
+template <typename K> struct Picked { K k = nullptr; int blk = 0, u = 0, depth = 0; };
+template <typename S> struct DiagBase { const S *base; int64_t stride; };
+template <typename S, int E> inline DiagBase<S> diag_base(const jh_blockop *op)
+{
+    return {op->diag_strided ? (const S *)op->blocks[0].coeff : nullptr, op->diag_stride_elems * E};
+}
 
 namespace jhb {
 // ---- jh_tall.hip

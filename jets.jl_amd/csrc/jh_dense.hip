@@ -1450,33 +1450,21 @@ int gemv_list(const jh_dense_item *items, int64_t nitems, int64_t max_out, int64
 
 int jh_launch_gemv(const void *A, int64_t nr, int64_t nc, int dtype, void *y, const void *x, int adjoint)
 {
-    switch (dtype) {
-    case JH_F32: return gemv<float, 1>(A, nr, nc, y, x, adjoint);
-    case JH_F64: return gemv<double, 1>(A, nr, nc, y, x, adjoint);
-    case JH_C32: return gemv<float, 2>(A, nr, nc, y, x, adjoint);
-    case JH_C64: return gemv<double, 2>(A, nr, nc, y, x, adjoint);
-    }
-    return jh_fail(JH_ERR_INVALID, "gemv: unknown dtype %d", dtype);
+    return jh_by_dtype(dtype, "gemv", [&](auto t) {
+        using T = decltype(t);
+        return gemv<typename T::S, T::E>(A, nr, nc, y, x, adjoint);
+    });
 }
 
 // all children of a tall operator of uniform dense blocks in one go (jh_blockop.hip); `aligned`: every matrix pointer on 16 bytes
 int jh_launch_gemv_batched(const jh_dev_block *dev_blocks, int64_t nchild, int64_t nr, int64_t nc, int dtype, void *y, const void *x,
                            int adjoint, bool aligned, bool wide, const int64_t *dev_row_off)
 {
-    if (wide)
-        switch (dtype) {
-        case JH_F32: return gemv_batched_wide<float, 1>(dev_blocks, nchild, nr, nc, y, x, adjoint, aligned);
-        case JH_F64: return gemv_batched_wide<double, 1>(dev_blocks, nchild, nr, nc, y, x, adjoint, aligned);
-        case JH_C32: return gemv_batched_wide<float, 2>(dev_blocks, nchild, nr, nc, y, x, adjoint, aligned);
-        case JH_C64: return gemv_batched_wide<double, 2>(dev_blocks, nchild, nr, nc, y, x, adjoint, aligned);
-        }
-    switch (dtype) {
-    case JH_F32: return gemv_batched<float, 1>(dev_blocks, nchild, nr, nc, y, x, adjoint, aligned, dev_row_off);
-    case JH_F64: return gemv_batched<double, 1>(dev_blocks, nchild, nr, nc, y, x, adjoint, aligned, dev_row_off);
-    case JH_C32: return gemv_batched<float, 2>(dev_blocks, nchild, nr, nc, y, x, adjoint, aligned, dev_row_off);
-    case JH_C64: return gemv_batched<double, 2>(dev_blocks, nchild, nr, nc, y, x, adjoint, aligned, dev_row_off);
-    }
-    return jh_fail(JH_ERR_INVALID, "gemv_batched: unknown dtype %d", dtype);
+    return jh_by_dtype(dtype, "gemv_batched", [&](auto t) {
+        using T = decltype(t);
+        if (wide) return gemv_batched_wide<typename T::S, T::E>(dev_blocks, nchild, nr, nc, y, x, adjoint, aligned);
+        return gemv_batched<typename T::S, T::E>(dev_blocks, nchild, nr, nc, y, x, adjoint, aligned, dev_row_off);
+    });
 }
 
 // every dense child of a mixed operator: one launch of the sequential (rows) kernel for the children whose product in this direction is
@@ -1485,26 +1473,20 @@ int jh_launch_gemv_batched(const jh_dev_block *dev_blocks, int64_t nchild, int64
 int jh_launch_gemv_mixed_all(const jh_dev_block *blocks, int64_t nrow, int64_t ncol, int64_t rows_max_out, int64_t cols_max_out, int dtype, void *slabs,
                              int64_t slab_stride, const void *x, int transposed, bool aligned, const int64_t *dev_row_off, const int64_t *dev_col_off)
 {
-    switch (dtype) {
-    case JH_F32: return gemv_mixed_all<float, 1>(blocks, nrow, ncol, rows_max_out, cols_max_out, slabs, slab_stride, x, transposed, aligned, dev_row_off, dev_col_off);
-    case JH_F64: return gemv_mixed_all<double, 1>(blocks, nrow, ncol, rows_max_out, cols_max_out, slabs, slab_stride, x, transposed, aligned, dev_row_off, dev_col_off);
-    case JH_C32: return gemv_mixed_all<float, 2>(blocks, nrow, ncol, rows_max_out, cols_max_out, slabs, slab_stride, x, transposed, aligned, dev_row_off, dev_col_off);
-    case JH_C64: return gemv_mixed_all<double, 2>(blocks, nrow, ncol, rows_max_out, cols_max_out, slabs, slab_stride, x, transposed, aligned, dev_row_off, dev_col_off);
-    }
-    return jh_fail(JH_ERR_INVALID, "gemv_mixed_all: unknown dtype %d", dtype);
+    return jh_by_dtype(dtype, "gemv_mixed_all", [&](auto t) {
+        using T = decltype(t);
+        return gemv_mixed_all<typename T::S, T::E>(blocks, nrow, ncol, rows_max_out, cols_max_out, slabs, slab_stride, x, transposed, aligned, dev_row_off, dev_col_off);
+    });
 }
 
 // the dense children of one direction and pass of a sparse / mixed operator from their list (jh_blockop_create builds it)
 int jh_launch_gemv_list(const jh_dense_item *items, int64_t nitems, int64_t max_out, int64_t max_in, int pass, int dtype, void *slabs, const void *x, int aligned,
                         void *direct_out, int add_found)
 {
-    switch (dtype) {
-    case JH_F32: return gemv_list<float, 1>(items, nitems, max_out, max_in, pass, slabs, x, aligned, direct_out, add_found);
-    case JH_F64: return gemv_list<double, 1>(items, nitems, max_out, max_in, pass, slabs, x, aligned, direct_out, add_found);
-    case JH_C32: return gemv_list<float, 2>(items, nitems, max_out, max_in, pass, slabs, x, aligned, direct_out, add_found);
-    case JH_C64: return gemv_list<double, 2>(items, nitems, max_out, max_in, pass, slabs, x, aligned, direct_out, add_found);
-    }
-    return jh_fail(JH_ERR_INVALID, "gemv_list: unknown dtype %d", dtype);
+    return jh_by_dtype(dtype, "gemv_list", [&](auto t) {
+        using T = decltype(t);
+        return gemv_list<typename T::S, T::E>(items, nitems, max_out, max_in, pass, slabs, x, aligned, direct_out, add_found);
+    });
 }
 
 extern "C" int jh_gemv(const void *A_device, int64_t nr, int64_t nc, int dtype, jh_bvec *y, const jh_bvec *x, int adjoint)

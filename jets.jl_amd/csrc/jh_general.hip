@@ -1343,13 +1343,10 @@ int dense_mixed_apply(const jh_blockop *op, void *out, const void *in, bool tran
 namespace jhb {
 int dense_mixed(const jh_blockop *op, void *out, const void *in, bool transposed, bool fmode)
 {
-    switch (op->dtype) {
-    case JH_F32: return dense_mixed_apply<float, 1>(op, out, in, transposed, fmode);
-    case JH_F64: return dense_mixed_apply<double, 1>(op, out, in, transposed, fmode);
-    case JH_C32: return dense_mixed_apply<float, 2>(op, out, in, transposed, fmode);
-    case JH_C64: return dense_mixed_apply<double, 2>(op, out, in, transposed, fmode);
-    }
-    return jh_fail(JH_ERR_INVALID, "dense_mixed: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "dense_mixed", [&](auto t) {
+        using T = decltype(t);
+        return dense_mixed_apply<typename T::S, T::E>(op, out, in, transposed, fmode);
+    });
 }
 }  // namespace jhb
 namespace {
@@ -1366,19 +1363,14 @@ int loop_small(const jh_blockop *op, void *out, const void *in, int transposed, 
     int64_t gx = (maxn + 255) / 256;
     if (gx > 65535) gx = 65535;
     hipStream_t st = jh_ctx().stream;
-#define JH_SMALL(S, E)                                                                                                     \
-    hipLaunchKernelGGL((k_block_loop_small<S, E>), dim3((unsigned)gx, (unsigned)nlines), dim3(256), 0, st, op->dev_blocks, op->dev_dims, \
-                       op->nrow, op->ncol, op->dev_row_off, op->dev_col_off, (S *)out, (const S *)in, transposed, fmode)
-    switch (op->dtype) {
-    case JH_F32: JH_SMALL(float, 1); break;
-    case JH_F64: JH_SMALL(double, 1); break;
-    case JH_C32: JH_SMALL(float, 2); break;
-    case JH_C64: JH_SMALL(double, 2); break;
-    default: return jh_fail(JH_ERR_INVALID, "loop_small: unknown dtype %d", op->dtype);
-    }
-#undef JH_SMALL
-    JH_CHECK_HIP(hipGetLastError());
-    return JH_OK;
+    return jh_by_dtype(op->dtype, "loop_small", [&](auto t) -> int {
+        using T = decltype(t);
+        using S = typename T::S;
+        hipLaunchKernelGGL((k_block_loop_small<S, T::E>), dim3((unsigned)gx, (unsigned)nlines), dim3(256), 0, st, op->dev_blocks, op->dev_dims,
+                           op->nrow, op->ncol, op->dev_row_off, op->dev_col_off, (S *)out, (const S *)in, transposed, fmode);
+        JH_CHECK_HIP(hipGetLastError());
+        return JH_OK;
+    });
 }
 }  // namespace jhb
 namespace {
@@ -1390,24 +1382,18 @@ namespace jhb {
 
 int general_fwd(const jh_blockop *op, void *d, const void *m, int fmode)
 {
-    switch (op->dtype) {
-    case JH_F32: return ::general_fwd<float, 1>(op, d, m, fmode);
-    case JH_F64: return ::general_fwd<double, 1>(op, d, m, fmode);
-    case JH_C32: return ::general_fwd<float, 2>(op, d, m, fmode);
-    case JH_C64: return ::general_fwd<double, 2>(op, d, m, fmode);
-    }
-    return jh_fail(JH_ERR_INVALID, "general forward: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "general forward", [&](auto t) {
+        using T = decltype(t);
+        return ::general_fwd<typename T::S, T::E>(op, d, m, fmode);
+    });
 }
 
 int general_adj(const jh_blockop *op, void *m, const void *d)
 {
-    switch (op->dtype) {
-    case JH_F32: return ::general_adj<float, 1>(op, m, d);
-    case JH_F64: return ::general_adj<double, 1>(op, m, d);
-    case JH_C32: return ::general_adj<float, 2>(op, m, d);
-    case JH_C64: return ::general_adj<double, 2>(op, m, d);
-    }
-    return jh_fail(JH_ERR_INVALID, "general adjoint: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "general adjoint", [&](auto t) {
+        using T = decltype(t);
+        return ::general_adj<typename T::S, T::E>(op, m, d);
+    });
 }
 
 }  // namespace jhb

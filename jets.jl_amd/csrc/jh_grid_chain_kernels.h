@@ -247,20 +247,16 @@ int launch_grid_chain(const jh_chain *ch, int prog, void *out, const void *in, i
 {
     const jh_blockop *op = ch->op;
     const int64_t n = op->row_len[0];
-#define JH_GRID_K(S, E, NS)                                                                                                                  \
-    switch (op->ncol) {                                                                                                                    \
-    case 2: return launch_grid_chain_k<S, E, NS, 2, MODE>(ch, prog, out, in, n * E, accumulate, first_elem, end_elem);                                              \
-    case 3: return launch_grid_chain_k<S, E, NS, 3, MODE>(ch, prog, out, in, n * E, accumulate, first_elem, end_elem);                                              \
-    default: return launch_grid_chain_k<S, E, NS, 4, MODE>(ch, prog, out, in, n * E, accumulate, first_elem, end_elem);                                             \
-    }
-    switch (op->dtype) {
-    case JH_F32: JH_GRID_K(float, 1, 4)
-    case JH_F64: JH_GRID_K(double, 1, 2)
-    case JH_C32: JH_GRID_K(float, 2, 4)
-    case JH_C64: JH_GRID_K(double, 2, 2)
-    }
-#undef JH_GRID_K
-    return jh_fail(JH_ERR_INVALID, "grid chain: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "grid chain", [&](auto t) {
+        using T = decltype(t);
+        using S = typename T::S;
+        constexpr int E = T::E, NS = T::NS;
+        switch (op->ncol) {
+        case 2: return launch_grid_chain_k<S, E, NS, 2, MODE>(ch, prog, out, in, n * E, accumulate, first_elem, end_elem);
+        case 3: return launch_grid_chain_k<S, E, NS, 3, MODE>(ch, prog, out, in, n * E, accumulate, first_elem, end_elem);
+        default: return launch_grid_chain_k<S, E, NS, 4, MODE>(ch, prog, out, in, n * E, accumulate, first_elem, end_elem);
+        }
+    });
 }
 
 }  // namespace

@@ -234,20 +234,16 @@ static int grid_chain_step_by_dtype(const jh_chain *ch, void *u, const void *v, 
 {
     const jh_blockop *op = ch->op;
     const int64_t n = op->row_len[0];
-#define JH_GCS_K(S, E, NS)                                                                                           \
-    switch (op->ncol) {                                                                                             \
-    case 2: return launch_grid_chain_step_k<S, E, NS, 2>(ch, u, v, w, n * E, alpha, beta, normsq, first_elem, end_elem);                    \
-    case 3: return launch_grid_chain_step_k<S, E, NS, 3>(ch, u, v, w, n * E, alpha, beta, normsq, first_elem, end_elem);                    \
-    default: return launch_grid_chain_step_k<S, E, NS, 4>(ch, u, v, w, n * E, alpha, beta, normsq, first_elem, end_elem);                   \
-    }
-    switch (op->dtype) {
-    case JH_F32: JH_GCS_K(float, 1, 4)
-    case JH_F64: JH_GCS_K(double, 1, 2)
-    case JH_C32: JH_GCS_K(float, 2, 4)
-    case JH_C64: JH_GCS_K(double, 2, 2)
-    }
-#undef JH_GCS_K
-    return jh_fail(JH_ERR_INVALID, "grid chain step: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "grid chain step", [&](auto t) {
+        using T = decltype(t);
+        using S = typename T::S;
+        constexpr int E = T::E, NS = T::NS;
+        switch (op->ncol) {
+        case 2: return launch_grid_chain_step_k<S, E, NS, 2>(ch, u, v, w, n * E, alpha, beta, normsq, first_elem, end_elem);
+        case 3: return launch_grid_chain_step_k<S, E, NS, 3>(ch, u, v, w, n * E, alpha, beta, normsq, first_elem, end_elem);
+        default: return launch_grid_chain_step_k<S, E, NS, 4>(ch, u, v, w, n * E, alpha, beta, normsq, first_elem, end_elem);
+        }
+    });
 }
 
 int grid_chain_step(const jh_chain *ch, void *u, const void *v, void *w, double alpha, double beta, double *normsq)

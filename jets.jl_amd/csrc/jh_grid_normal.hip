@@ -292,13 +292,10 @@ int grid_words_ensure(const jh_blockop *op)
 static int grid_normal_by_dtype(const jh_blockop *op, void *y, const void *m, int64_t first_elem, int64_t end_elem)
 {
     JH_TRY(grid_words_ensure(op));                            // the packed table of a mixed grid, row-major (N x K words), built on first use
-    switch (op->dtype) {
-    case JH_F32: return grid_normal_k<float, 1, 4>(op, y, m, first_elem, end_elem);
-    case JH_F64: return grid_normal_k<double, 1, 2>(op, y, m, first_elem, end_elem);
-    case JH_C32: return grid_normal_k<float, 2, 4>(op, y, m, first_elem, end_elem);
-    case JH_C64: return grid_normal_k<double, 2, 2>(op, y, m, first_elem, end_elem);
-    default: return jh_fail(JH_ERR_INVALID, "grid_normal: unknown dtype %d", op->dtype);
-    }
+    return jh_by_dtype(op->dtype, "grid_normal", [&](auto t) {
+        using T = decltype(t);
+        return grid_normal_k<typename T::S, T::E, T::NS>(op, y, m, first_elem, end_elem);
+    });
 }
 
 int grid_normal(const jh_blockop *op, void *y, const void *m) { return grid_normal_by_dtype(op, y, m, 0, -1); }

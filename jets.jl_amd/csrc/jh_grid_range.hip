@@ -182,13 +182,10 @@ int grid_range_bounds(const jh_blockop *op, int64_t first_elem, int64_t count, c
 int grid_adj_range(const jh_blockop *op, void *m, const void *d, int64_t first_elem, int64_t count)
 {
     JH_TRY(grid_words_ensure(op));
-    switch (op->dtype) {
-    case JH_F32: return grid_adj_k<float, 1, 4>(op, m, d, first_elem, first_elem + count);
-    case JH_F64: return grid_adj_k<double, 1, 2>(op, m, d, first_elem, first_elem + count);
-    case JH_C32: return grid_adj_k<float, 2, 4>(op, m, d, first_elem, first_elem + count);
-    case JH_C64: return grid_adj_k<double, 2, 2>(op, m, d, first_elem, first_elem + count);
-    default: return jh_fail(JH_ERR_INVALID, "grid adjoint: unknown dtype %d", op->dtype);
-    }
+    return jh_by_dtype(op->dtype, "grid adjoint", [&](auto t) {
+        using T = decltype(t);
+        return grid_adj_k<typename T::S, T::E, T::NS>(op, m, d, first_elem, first_elem + count);
+    });
 }
 
 }  // namespace jhb

@@ -259,13 +259,10 @@ bool grid_step_ok(const jh_blockop *op, const void *u, const void *v, const void
 static int grid_step_by_dtype(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq, int64_t first_elem, int64_t end_elem)
 {
     JH_TRY(grid_words_ensure(op));
-    switch (op->dtype) {
-    case JH_F32: return grid_step_k<float, 1, 4>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
-    case JH_F64: return grid_step_k<double, 1, 2>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
-    case JH_C32: return grid_step_k<float, 2, 4>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
-    case JH_C64: return grid_step_k<double, 2, 2>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
-    default: return jh_fail(JH_ERR_INVALID, "grid step: unknown dtype %d", op->dtype);
-    }
+    return jh_by_dtype(op->dtype, "grid step", [&](auto t) {
+        using T = decltype(t);
+        return grid_step_k<typename T::S, T::E, T::NS>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
+    });
 }
 
 int grid_step(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq)

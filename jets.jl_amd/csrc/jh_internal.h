@@ -163,6 +163,20 @@ static inline size_t jh_dtype_size(int dtype)
     }
 }
 static inline bool jh_dtype_complex(int dtype) { return dtype == JH_C32 || dtype == JH_C64; }
+// An element type as the kernels' template arguments: the scalar S, E scalars per element, NS scalars per 16-byte pack.
+// jh_by_dtype(dtype, who, f) calls f(tag) for the matching type -- f is a generic lambda that reads `typename decltype(t)::S`,
+// `decltype(t)::E`, `decltype(t)::NS` -- and returns what f returns.
+template <typename S_, int E_, int NS_> struct jh_elem { using S = S_; static constexpr int E = E_, NS = NS_; };
+template <class F> inline int jh_by_dtype(int dtype, const char *who, F &&f)
+{
+    switch (dtype) {
+    case JH_F32: return f(jh_elem<float, 1, 4>{});
+    case JH_F64: return f(jh_elem<double, 1, 2>{});
+    case JH_C32: return f(jh_elem<float, 2, 4>{});
+    case JH_C64: return f(jh_elem<double, 2, 2>{});
+    default: return jh_fail(JH_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
+    }
+}
 
 struct jh_bvec {
     int ctx = -1;                       // the context it was created in

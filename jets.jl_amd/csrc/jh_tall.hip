@@ -622,12 +622,24 @@ int launch_fold_parts(const void *parts, int64_t part_stride, int64_t nparts, vo
     return JH_OK;
 }
 
+// the all-diagonal forward's instantiations of one workgroup size and load policy: 1, 2, 4 or 8 packs per lane
+template <typename S, int E, int NS, bool NT, int BLK>
+Picked<decltype(&k_tall_diag_fwd<S, E, NS, 1, NT, BLK>)> pick_tall_fwd(int unroll)
+{
+    switch (unroll) {
+    case 1: return {&k_tall_diag_fwd<S, E, NS, 1, NT, BLK>, BLK, 1, 0};
+    case 2: return {&k_tall_diag_fwd<S, E, NS, 2, NT, BLK>, BLK, 2, 0};
+    case 4: return {&k_tall_diag_fwd<S, E, NS, 4, NT, BLK>, BLK, 4, 0};
+    case 8: return {&k_tall_diag_fwd<S, E, NS, 8, NT, BLK>, BLK, 8, 0};
+    default: return {};
+    }
+}
+
 template <typename S, int E, int NS, bool NT, int BLK>
 int launch_tall_fwd_u(const jh_blockop *op, void *d, const void *m, int64_t n_scalars, const TallShape &sh)
 {
     jh_context &c = jh_ctx();
-    const S *a_base = op->diag_strided ? (const S *)op->blocks[0].coeff : nullptr;
-    const int64_t a_stride = op->diag_stride_elems * E;
+    const DiagBase<S> a = diag_base<S, E>(op);
     int64_t G = sh.aux;
     if (G > op->nrow) G = op->nrow;
     int64_t gy = (op->nrow + G - 1) / G;
@@ -639,33 +651,49 @@ int launch_tall_fwd_u(const jh_blockop *op, void *d, const void *m, int64_t n_sc
     if (band > gy) band = gy;
     c.last_fwd_walk = sh.ctiles ? 2 : sh.order;
     c.last_fwd_rows_per_wg = G;
-#define JH_FWD_CASE(U)                                                                                               \
-    case U: {                                                                                                         \
-        int64_t gx = (n_scalars + (int64_t)U * BLK * NS - 1) / ((int64_t)U * BLK * NS);                               \
-        JH_REQUIRE(gx * gy * BLK < (int64_t)1 << 32, "tall forward: grid of %lld workgroups is too large", (long long)(gx * gy)); \
-        hipLaunchKernelGGL((k_tall_diag_fwd<S, E, NS, U, NT, BLK>), dim3((unsigned)(gx * gy)), dim3(BLK), 0, c.stream, \
-                           op->dev_blocks, op->nrow, (int)G, a_base, a_stride, (const S *)m, (S *)d, n_scalars,      \
-                           (unsigned)gx, (unsigned)gy, (unsigned)band, (unsigned)sh.ctiles);                       \
-    } break;
-    switch (sh.unroll) {
-        JH_FWD_CASE(1)
-        JH_FWD_CASE(2)
-        JH_FWD_CASE(4)
-        JH_FWD_CASE(8)
-    default: return jh_fail(JH_ERR_INVALID, "fwd_unroll %d unsupported", sh.unroll);
-    }
-#undef JH_FWD_CASE
+    const auto k = pick_tall_fwd<S, E, NS, NT, BLK>(sh.unroll);
+    if (!k.k) return jh_fail(JH_ERR_INVALID, "fwd_unroll %d unsupported", sh.unroll);
+    JH_REQUIRE(k.blk == BLK && k.u == sh.unroll, "tall forward: picked %d x %d for rows grouped for %d x %d", k.blk, k.u, BLK, sh.unroll);   // (G, gy above)
+    const int64_t gx = (n_scalars + (int64_t)k.u * k.blk * NS - 1) / ((int64_t)k.u * k.blk * NS);
+    JH_REQUIRE(gx * gy * k.blk < (int64_t)1 << 32, "tall forward: grid of %lld workgroups is too large", (long long)(gx * gy));
+    hipLaunchKernelGGL(k.k, dim3((unsigned)(gx * gy)), dim3(k.blk), 0, c.stream, op->dev_blocks, op->nrow, (int)G, a.base, a.stride, (const S *)m, (S *)d,
+                       n_scalars, (unsigned)gx, (unsigned)gy, (unsigned)band, (unsigned)sh.ctiles, 0);
     JH_CHECK_HIP(hipGetLastError());
     return JH_OK;
 }
+
+// the all-diagonal ordered walk's instantiations of one workgroup size, mode and load policy: first match of (packs per lane, rows in flight)
+template <typename S, int E, int NS, bool NT, int MODE, int BLK> struct TallAdjPicker {
+    using Kernel = decltype(&k_tall_diag_adj<S, E, NS, 1, 4, NT, MODE, BLK>);
+    int unroll, depth;
+    Picked<Kernel> got;
+    template <int U, int DEPTH> bool row()
+    {
+        if constexpr (jhb::adj_shape_built(MODE, BLK, U, DEPTH))
+            if (unroll == U && depth == DEPTH) {
+                got = {&k_tall_diag_adj<S, E, NS, U, DEPTH, NT, MODE, BLK>, BLK, U, DEPTH};
+                return true;
+            }
+        return false;
+    }
+    Picked<Kernel> pick()
+    {
+        // (round 6: of this list only the combinations with a workgroup size that the size rule can select -- adj_shape_built)
+        // Round 5: the six (packs per lane, rows in flight) shapes the size rule of pick_adj_shape can select.  Five more used to be compiled
+        // for the knobs alone -- (1,1) (1,2) (2,1) (2,2) (4,1): 240 of this kernel's 524 instantiations, the bulk of the library's build
+        // time -- and lost every sweep of rounds 1-2 (profiles/sweep_r02_adj_rows.txt); pick_adj_shape now maps a knob pair to the nearest
+        // shape of this list (same bits: the rows are summed in order whatever the shape).
+        (void)(row<1, 4>() || row<1, 8>() || row<2, 4>() || row<2, 8>() || row<4, 2>() || row<4, 4>());
+        return got;
+    }
+};
 
 template <typename S, int E, int NS, bool NT, int MODE, int BLK>
 int launch_tall_adj_u(const jh_blockop *op, void *out, const void *in, int64_t n_scalars, const TallShape &sh, int64_t s_begin,
                       int64_t s_end)
 {
     jh_context &c = jh_ctx();
-    const S *a_base = op->diag_strided ? (const S *)op->blocks[0].coeff : nullptr;
-    const int64_t a_stride = op->diag_stride_elems * E;
+    const DiagBase<S> a = diag_base<S, E>(op);
     const int direct = (op->nrow == 1 && MODE == 0) ? 1 : 0;
     // A 128 GiB walk runs 2-3 % faster as two launches over 512 rows each than as one (profiles/exp_r01_adj_row_chunks.txt,
     // exp_r01_adj_by_rows.txt); the second launch continues the ordered sum, so the bits do not change.
@@ -688,31 +716,19 @@ int launch_tall_adj_u(const jh_blockop *op, void *out, const void *in, int64_t n
         c.last_adj_launches = 1;
     }
     c.last_adj_parts = parts;
-#define JH_ADJ_CASE(U, DEPTH)                                                                                          \
-    if constexpr (jhb::adj_shape_built(MODE, BLK, U, DEPTH))                                                           \
-    if (sh.unroll == U && sh.aux == DEPTH) {                                                                           \
-        int64_t gx = (s_end - s_begin + (int64_t)U * BLK * NS - 1) / ((int64_t)U * BLK * NS);                          \
-        for (int64_t r0 = 0; r0 < op->nrow; r0 += rows_per_launch) {                                                   \
-            const int64_t r1 = r0 + rows_per_launch < op->nrow ? r0 + rows_per_launch : op->nrow;                        \
-            hipLaunchKernelGGL((k_tall_diag_adj<S, E, NS, U, DEPTH, NT, MODE, BLK>), dim3((unsigned)gx, (unsigned)parts), \
-                               dim3(BLK), 0,                                                                           \
-                               c.stream, op->dev_blocks, op->nrow, a_base, a_stride, (S *)out, (const S *)in, n_scalars,   \
-                               direct, s_begin, s_end, r0, r1, (r0 > 0 || from_found) ? 1 : 0, rows_per_part, (S *)slabs, part_stride); \
-            JH_CHECK_HIP(hipGetLastError());                                                                           \
-        }                                                                                                              \
-        if (parts > 1) return launch_fold_parts<S, NS>(slabs, part_stride, parts, out, s_begin, s_end);                \
-        return JH_OK;                                                                                                  \
+    const auto k = TallAdjPicker<S, E, NS, NT, MODE, BLK>{sh.unroll, sh.aux, {}}.pick();
+    if (!k.k) return jh_fail(JH_ERR_INVALID, "adj_unroll %d x adj_depth %d unsupported", sh.unroll, sh.aux);
+    JH_REQUIRE(k.blk == BLK && k.u == sh.unroll, "tall adjoint: picked %d x %d for parts sized for %d x %d", k.blk, k.u, BLK, sh.unroll);   // (gx0 above)
+    const int64_t gx = (s_end - s_begin + (int64_t)k.u * k.blk * NS - 1) / ((int64_t)k.u * k.blk * NS);
+    for (int64_t r0 = 0; r0 < op->nrow; r0 += rows_per_launch) {
+        const int64_t r1 = r0 + rows_per_launch < op->nrow ? r0 + rows_per_launch : op->nrow;
+        hipLaunchKernelGGL(k.k, dim3((unsigned)gx, (unsigned)parts), dim3(k.blk), 0, c.stream, op->dev_blocks, op->nrow, a.base, a.stride, (S *)out,
+                           (const S *)in, n_scalars, direct, s_begin, s_end, r0, r1, (r0 > 0 || from_found) ? 1 : 0, rows_per_part, (S *)slabs, part_stride,
+                           (S)1);
+        JH_CHECK_HIP(hipGetLastError());
     }
-    // (round 6: of this list only the combinations with a workgroup size that the size rule can select -- adj_shape_built)
-    // Round 5: the six (packs per lane, rows in flight) shapes the size rule of pick_adj_shape can select.  Five more used to be compiled
-    // for the knobs alone -- (1,1) (1,2) (2,1) (2,2) (4,1): 240 of this kernel's 524 instantiations, the bulk of the library's build
-    // time -- and lost every sweep of rounds 1-2 (profiles/sweep_r02_adj_rows.txt); pick_adj_shape now maps a knob pair to the nearest
-    // shape of this list (same bits: the rows are summed in order whatever the shape).
-    JH_ADJ_CASE(1, 4) JH_ADJ_CASE(1, 8)
-    JH_ADJ_CASE(2, 4) JH_ADJ_CASE(2, 8)
-    JH_ADJ_CASE(4, 2) JH_ADJ_CASE(4, 4)
-#undef JH_ADJ_CASE
-    return jh_fail(JH_ERR_INVALID, "adj_unroll %d x adj_depth %d unsupported", sh.unroll, sh.aux);
+    if (parts > 1) return launch_fold_parts<S, NS>(slabs, part_stride, parts, out, s_begin, s_end);
+    return JH_OK;
 }
 
 template <typename S, int E, int NS>
@@ -1177,17 +1193,16 @@ int launch_tall_fwd_mixed(const jh_blockop *op, void *d, const void *m, int64_t 
     }
     c.last_fwd_walk = ctiles ? 2 : 0;
     c.last_fwd_rows_per_wg = G;
-#define JH_FWD_MIXED(NTV)                                                                                                                   \
-    hipLaunchKernelGGL((k_tall_diag_fwd<S, E, NS, U, NTV, BLK, true>), dim3((unsigned)(gx * gy)), dim3(BLK), 0, c.stream, op->dev_blocks,        \
-                       nrows, (int)G, listed ? reinterpret_cast<const S *>(op->dev_rows_nz) : (const S *)nullptr, (int64_t)(listed ? -1 : 0), (const S *)m, (S *)d, \
-                       n_scalars, (unsigned)gx, (unsigned)gy, 1u, (unsigned)ctiles, fmode)
     // Rows off the 16-byte grid take TEMPORAL LOADS: a 128-byte line that two neighbouring waves share is then still in L2 when the second one asks --
     // streamed, it came from HBM twice (forward 256 x 255^3 5.82 -> 5.92 TB/s, 512 x 127^3 5.02 -> 5.11, 1024 x 101^3 5.30 -> 5.47; aligned rows: no
     // difference either way; profiles/bench_unaligned_r05.txt).  The STORES stay streaming stores (k_tall_diag_fwd).  Knob ua_nt: -1 this rule,
     // 0 / 1 temporal / nontemporal loads always.
     const bool off_grid = (n_scalars * (int64_t)sizeof(S)) % 16 != 0 || !op->coeff_aligned16 || ((((uintptr_t)d) | ((uintptr_t)m)) & 15u) != 0;
-    if (c.ua_nt == 0 || (c.ua_nt < 0 && off_grid)) JH_FWD_MIXED(false); else JH_FWD_MIXED(true);
-#undef JH_FWD_MIXED
+    const bool temporal = c.ua_nt == 0 || (c.ua_nt < 0 && off_grid);
+    const auto k = temporal ? &k_tall_diag_fwd<S, E, NS, U, false, BLK, true> : &k_tall_diag_fwd<S, E, NS, U, true, BLK, true>;
+    hipLaunchKernelGGL(k, dim3((unsigned)(gx * gy)), dim3(BLK), 0, c.stream, op->dev_blocks, nrows, (int)G,
+                       listed ? reinterpret_cast<const S *>(op->dev_rows_nz) : (const S *)nullptr, (int64_t)(listed ? -1 : 0), (const S *)m, (S *)d, n_scalars,
+                       (unsigned)gx, (unsigned)gy, 1u, (unsigned)ctiles, fmode);
     JH_CHECK_HIP(hipGetLastError());
     return JH_OK;
 }
@@ -1212,20 +1227,17 @@ int launch_tall_adj_mixed_u(const jh_blockop *op, void *out, const void *in, int
     }
     c.last_adj_parts = parts;
     c.last_adj_launches = 1;
-#define JH_ADJ_MIXED(NTV)                                                                                                                   \
-    hipLaunchKernelGGL((k_tall_diag_adj<S, E, NS, U, DEPTH, NTV, MODE, BLK, true, TAIL>), dim3((unsigned)gx, (unsigned)parts), dim3(BLK), 0, c.stream, \
-                       op->dev_blocks, op->nrow, (const S *)nullptr, (int64_t)0, (S *)out, (const S *)in, n_scalars, 0, s_begin, s_end,            \
-                       (int64_t)0, op->nrow, from_found, rows_per_part, (S *)slabs, part_stride, (S)(MODE == 0 ? c.adj_in_scale : 1.0))
     // (rows off the 16-byte grid: temporal loads, see launch_tall_fwd_mixed -- from 32 MiB rows on: 256 x 255^3 adjoint 5.83 -> 6.17 TB/s, but 512 x 127^3
     // 5.97 -> 5.73 and 1024 x 101^3 5.70 -> 5.67 on the same boxes)
     const bool off_grid = (n_scalars * (int64_t)sizeof(S)) % 16 != 0 || !op->coeff_aligned16 || ((((uintptr_t)out) | ((uintptr_t)in)) & 15u) != 0;
     // (the shape without the partial-pack logic only ever sees aligned rows: no temporal instantiation of it)
+    auto k = &k_tall_diag_adj<S, E, NS, U, DEPTH, true, MODE, BLK, true, TAIL>;
     if constexpr (TAIL) {
-        if (c.ua_nt == 0 || (c.ua_nt < 0 && off_grid && n_scalars * (int64_t)sizeof(S) >= ((int64_t)32 << 20))) JH_ADJ_MIXED(false); else JH_ADJ_MIXED(true);
-    } else {
-        JH_ADJ_MIXED(true);
+        if (c.ua_nt == 0 || (c.ua_nt < 0 && off_grid && n_scalars * (int64_t)sizeof(S) >= ((int64_t)32 << 20))) k = &k_tall_diag_adj<S, E, NS, U, DEPTH, false, MODE, BLK, true, TAIL>;
     }
-#undef JH_ADJ_MIXED
+    hipLaunchKernelGGL(k, dim3((unsigned)gx, (unsigned)parts), dim3(BLK), 0, c.stream, op->dev_blocks, op->nrow, (const S *)nullptr, (int64_t)0, (S *)out,
+                       (const S *)in, n_scalars, 0, s_begin, s_end, (int64_t)0, op->nrow, from_found, rows_per_part, (S *)slabs, part_stride,
+                       (S)(MODE == 0 ? c.adj_in_scale : 1.0));
     JH_CHECK_HIP(hipGetLastError());
     if (parts > 1) return launch_fold_parts<S, NS>(slabs, part_stride, parts, out, s_begin, s_end);
     return JH_OK;
@@ -1270,29 +1282,22 @@ int launch_tall_adj_mixed(const jh_blockop *op, void *out, const void *in, int64
 
 namespace jhb {
 
-#define JH_BY_DTYPE(CALL)                                                  \
-    switch (op->dtype) {                                                   \
-    case JH_F32: return CALL(float, 1, 4);                                 \
-    case JH_F64: return CALL(double, 1, 2);                                \
-    case JH_C32: return CALL(float, 2, 4);                                 \
-    case JH_C64: return CALL(double, 2, 2);                                \
-    }                                                                      \
-    return jh_fail(JH_ERR_INVALID, "unknown dtype %d", op->dtype)
-
 int tall_fwd(const jh_blockop *op, void *d, const void *m)
 {
     const int64_t n = op->row_len[0];
-#define JH_CALL(S, E, NS) launch_tall_fwd<S, E, NS>(op, d, m, n * E)
-    JH_BY_DTYPE(JH_CALL);
-#undef JH_CALL
+    return jh_by_dtype(op->dtype, "tall forward", [&](auto t) {
+        using T = decltype(t);
+        return launch_tall_fwd<typename T::S, T::E, T::NS>(op, d, m, n * T::E);
+    });
 }
 
 int tall_fwd_mixed(const jh_blockop *op, void *d, const void *m, int fmode)
 {
     const int64_t n = op->row_len[0];
-#define JH_CALL(S, E, NS) launch_tall_fwd_mixed<S, E, NS>(op, d, m, n * E, fmode)
-    JH_BY_DTYPE(JH_CALL);
-#undef JH_CALL
+    return jh_by_dtype(op->dtype, "tall forward", [&](auto t) {
+        using T = decltype(t);
+        return launch_tall_fwd_mixed<typename T::S, T::E, T::NS>(op, d, m, n * T::E, fmode);
+    });
 }
 
 int tall_adj(const jh_blockop *op, void *out, const void *in, int mode, bool mixed, int64_t first_elem, int64_t end_elem)
@@ -1303,13 +1308,14 @@ int tall_adj(const jh_blockop *op, void *out, const void *in, int mode, bool mix
         JH_TRY(bare_chain(op, out, in, mode, &took));
         if (took) return JH_OK;
     }
-#define JH_CALL(S, E, NS)                                                                                                                    \
-    (mode == 0 ? (mixed ? launch_tall_adj_mixed<S, E, NS, 0>(op, out, in, n * E, first_elem * E, end_elem < 0 ? -1 : end_elem * E)           \
-                        : launch_tall_adj<S, E, NS, 0>(op, out, in, n * E, first_elem * E, end_elem < 0 ? -1 : end_elem * E))                 \
-               : (mixed ? launch_tall_adj_mixed<S, E, NS, 1>(op, out, in, n * E, first_elem * E, end_elem < 0 ? -1 : end_elem * E)           \
-                        : launch_tall_adj<S, E, NS, 1>(op, out, in, n * E, first_elem * E, end_elem < 0 ? -1 : end_elem * E)))
-    JH_BY_DTYPE(JH_CALL);
-#undef JH_CALL
+    return jh_by_dtype(op->dtype, "tall adjoint", [&](auto t) {
+        using T = decltype(t);
+        using S = typename T::S;
+        constexpr int E = T::E, NS = T::NS;
+        const int64_t lo = first_elem * E, hi = end_elem < 0 ? -1 : end_elem * E;
+        if (mode == 0) return mixed ? launch_tall_adj_mixed<S, E, NS, 0>(op, out, in, n * E, lo, hi) : launch_tall_adj<S, E, NS, 0>(op, out, in, n * E, lo, hi);
+        return mixed ? launch_tall_adj_mixed<S, E, NS, 1>(op, out, in, n * E, lo, hi) : launch_tall_adj<S, E, NS, 1>(op, out, in, n * E, lo, hi);
+    });
 }
 
 int fold_parts(int dtype, const void *parts, int64_t part_stride, int64_t nparts, void *out, int64_t s_begin, int64_t s_end)
@@ -1324,7 +1330,6 @@ int split_adjoint_tmp(const jh_blockop *op, void **tmp)
     if (op->dtype == JH_F32 || op->dtype == JH_C32) return ::split_adjoint_tmp<float, 4>(op, ns, op->dtype == JH_C32, tmp);
     return ::split_adjoint_tmp<double, 2>(op, ns, false, tmp);
 }
-#undef JH_BY_DTYPE
 
 }  // namespace jhb
 
@@ -1340,6 +1345,19 @@ bool jh_blockop_tall_step_ok(const jh_blockop *op, const void *rng_ptr, const vo
     return jh_blockop_tall_fast(op, rng_ptr, dom_ptr) || (tall_unaligned_ok(op, rng_ptr, dom_ptr) && !(op->nonlinear && !op->pointed));
 }
 
+// the fused CG pass' instantiations: launch-bound domains thin workgroups with eight rows in flight (shape 0); from 2 MiB blocks on the fused normal
+// operator's shapes (1: 512 x 2 x 2, 2: 1024 x 4 x 4 -- ComplexF32 two rows: registers)
+template <typename S, int E, int NS>
+static Picked<decltype(&k_cg_normal<S, E, NS, 8>)> pick_cg_normal(int shape, bool nt)
+{
+    constexpr int D2 = (E == 2 && sizeof(S) == 4) ? 2 : 4;
+    if (shape == 2) return {&k_cg_normal<S, E, NS, D2, 1024, 4, true>, 1024, 4, D2};
+    if (shape == 1 && nt) return {&k_cg_normal<S, E, NS, 2, 512, 2, true>, 512, 2, 2};
+    if (shape == 1) return {&k_cg_normal<S, E, NS, 2, 512, 2, false>, 512, 2, 2};
+    if (nt) return {&k_cg_normal<S, E, NS, 8, 256, 1, true>, 256, 1, 8};
+    return {&k_cg_normal<S, E, NS, 8, 256, 1, false>, 256, 1, 8};
+}
+
 // all-DIAG tall operators only (the caller checks: jh_lsqr.hip, cg_graph_impl); one pack per lane, 8 rows in flight
 int jh_launch_cg_normal(const jh_blockop *op, jh_bvec *p, const jh_bvec *s, jh_bvec *y, const jh_cg_dev *st, double *partials, int64_t *nparts)
 {
@@ -1353,29 +1371,20 @@ int jh_launch_cg_normal(const jh_blockop *op, jh_bvec *p, const jh_bvec *s, jh_b
     const int64_t grid = (packs + per_wg - 1) / per_wg;
     JH_REQUIRE(grid >= 1 && grid < ((int64_t)1 << 22), "cg normal pass: domain of %lld elements is out of range", (long long)n);
     *nparts = grid;
-#define JH_CGN_S(S, E, NS, DEPTH, BLK, U, NTV)                                                                                                  \
-    hipLaunchKernelGGL((k_cg_normal<S, E, NS, DEPTH, BLK, U, NTV>), dim3((unsigned)grid), dim3(BLK), 0, c.stream, op->dev_blocks, op->nrow,      \
-                       op->diag_strided ? (const S *)op->blocks[0].coeff : (const S *)nullptr, op->diag_stride_elems * E, (S *)p->data,          \
-                       (const S *)s->data, (S *)y->data, n * E, st, partials)
     // the coefficients of an operator that an iteration re-reads and that fit the Infinity Cache are loaded TEMPORAL (jh_stream_nt)
     const bool nt = jh_stream_nt(2.0 * (double)op->nrow * (double)n * (double)jh_dtype_size(op->dtype));
-#define JH_CGN(S, E, NS)                                                                                                                        \
-    do {                                                                                                                                        \
-        if (shape == 2) JH_CGN_S(S, E, NS, ((E == 2 && sizeof(S) == 4) ? 2 : 4), 1024, 4, true);                                                \
-        else if (shape == 1) { if (nt) JH_CGN_S(S, E, NS, 2, 512, 2, true); else JH_CGN_S(S, E, NS, 2, 512, 2, false); }                        \
-        else { if (nt) JH_CGN_S(S, E, NS, 8, 256, 1, true); else JH_CGN_S(S, E, NS, 8, 256, 1, false); }                                        \
-    } while (0)
-    switch (op->dtype) {
-    case JH_F32: JH_CGN(float, 1, 4); break;
-    case JH_F64: JH_CGN(double, 1, 2); break;
-    case JH_C32: JH_CGN(float, 2, 4); break;
-    case JH_C64: JH_CGN(double, 2, 2); break;
-    default: return jh_fail(JH_ERR_INVALID, "cg normal pass: unknown dtype %d", op->dtype);
-    }
-#undef JH_CGN_S
-#undef JH_CGN
-    JH_CHECK_HIP(hipGetLastError());
-    return JH_OK;
+    return jh_by_dtype(op->dtype, "cg normal pass", [&](auto t) -> int {
+        using T = decltype(t);
+        using S = typename T::S;
+        constexpr int E = T::E, NS = T::NS;
+        const auto k = pick_cg_normal<S, E, NS>(shape, nt);
+        JH_REQUIRE(k.k && (int64_t)k.blk * k.u == per_wg, "cg normal pass: no kernel of %lld packs per workgroup", (long long)per_wg);   // (grid is sized for per_wg)
+        const DiagBase<S> a = diag_base<S, E>(op);
+        hipLaunchKernelGGL(k.k, dim3((unsigned)grid), dim3(k.blk), 0, c.stream, op->dev_blocks, op->nrow, a.base, a.stride, (S *)p->data, (const S *)s->data,
+                           (S *)y->data, n * E, st, partials);
+        JH_CHECK_HIP(hipGetLastError());
+        return JH_OK;
+    });
 }
 
 extern "C" {

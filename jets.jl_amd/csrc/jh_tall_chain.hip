@@ -246,15 +246,10 @@ int jh_chain_apply(const jh_chain *ch, jh_bvec *out, const jh_bvec *x, int accum
     const int64_t n = op->row_len[0];
     if (ch->type == JH_CHAIN_ADJOINT) return jhb::chain_launch_adjoint(ch, out->data, x->data, accumulate, 0, out->length);
     if (ch->type == JH_CHAIN_NORMAL) return jhb::chain_launch_normal(ch, out->data, x->data, accumulate, 0, out->length);
-#define JH_CHAIN_CALL(S, E, NS) launch_chain_fwd<S, E, NS>(ch, out->data, x->data, n * E, accumulate)
-    switch (op->dtype) {
-    case JH_F32: return JH_CHAIN_CALL(float, 1, 4);
-    case JH_F64: return JH_CHAIN_CALL(double, 1, 2);
-    case JH_C32: return JH_CHAIN_CALL(float, 2, 4);
-    case JH_C64: return JH_CHAIN_CALL(double, 2, 2);
-    }
-#undef JH_CHAIN_CALL
-    return jh_fail(JH_ERR_INVALID, "jh_chain_apply: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "jh_chain_apply", [&](auto t) {
+        using T = decltype(t);
+        return launch_chain_fwd<typename T::S, T::E, T::NS>(ch, out->data, x->data, n * T::E, accumulate);
+    });
 }
 
 // The ADJOINT / NORMAL chain over the domain's elements [first_elem, first_elem + count): what a host pipelining the exchange of the domain vector range

@@ -8,31 +8,24 @@ int chain_launch_adjoint(const jh_chain *ch, void *out, const void *in, int accu
     const ChainArgs &args = ca ? *ca : ch->args;
     const jh_blockop *op = ch->op;
     const int64_t n = op->row_len[0];
-    switch (op->dtype) {
-    case JH_F32: return launch_chain_adj<float, 1, 4, 0>(ch, args, out, in, n, accumulate, first_elem, end_elem);
-    case JH_F64: return launch_chain_adj<double, 1, 2, 0>(ch, args, out, in, n, accumulate, first_elem, end_elem);
-    case JH_C32: return launch_chain_adj<float, 2, 4, 0>(ch, args, out, in, n * 2, accumulate, first_elem * 2, end_elem * 2);
-    case JH_C64: return launch_chain_adj<double, 2, 2, 0>(ch, args, out, in, n * 2, accumulate, first_elem * 2, end_elem * 2);
-    }
-    return jh_fail(JH_ERR_INVALID, "chain_launch_adjoint: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "chain_launch_adjoint", [&](auto t) {
+        using T = decltype(t);
+        return launch_chain_adj<typename T::S, T::E, T::NS, 0>(ch, args, out, in, n * T::E, accumulate, first_elem * T::E, end_elem * T::E);
+    });
 }
 
 // out = accumulate(out, Q(folded)) over the scalars [s_begin, s_end) of a domain vector: the split walk's last step, for the grid chains too
 int chain_finish(const jh_chain *ch, const ChainArgs &ca, void *out, const void *folded, int64_t s_begin, int64_t s_end, int accumulate)
 {
     jh_context &c = jh_ctx();
-#define JH_FINISH(S, E, NS)                                                                                                                  \
-    hipLaunchKernelGGL((k_chain_finish<S, E, NS>), dim3((unsigned)(((s_end - s_begin + NS - 1) / NS + 255) / 256)), dim3(256), 0, c.stream, ca, (S *)out, \
-                       (const S *)folded, s_begin, s_end, accumulate)
-    switch (ch->op->dtype) {
-    case JH_F32: JH_FINISH(float, 1, 4); break;
-    case JH_F64: JH_FINISH(double, 1, 2); break;
-    case JH_C32: JH_FINISH(float, 2, 4); break;
-    case JH_C64: JH_FINISH(double, 2, 2); break;
-    default: return jh_fail(JH_ERR_INVALID, "chain_finish: unknown dtype %d", ch->op->dtype);
-    }
-#undef JH_FINISH
-    JH_CHECK_HIP(hipGetLastError());
-    return JH_OK;
+    return jh_by_dtype(ch->op->dtype, "chain_finish", [&](auto t) -> int {
+        using T = decltype(t);
+        using S = typename T::S;
+        constexpr int NS = T::NS;
+        hipLaunchKernelGGL((k_chain_finish<S, T::E, NS>), dim3((unsigned)(((s_end - s_begin + NS - 1) / NS + 255) / 256)), dim3(256), 0, c.stream, ca, (S *)out,
+                           (const S *)folded, s_begin, s_end, accumulate);
+        JH_CHECK_HIP(hipGetLastError());
+        return JH_OK;
+    });
 }
 }  // namespace jhb

@@ -8,12 +8,9 @@ int chain_launch_normal(const jh_chain *ch, void *out, const void *in, int accum
     const ChainArgs &args = ca ? *ca : ch->args;
     const jh_blockop *op = ch->op;
     const int64_t n = op->row_len[0];
-    switch (op->dtype) {
-    case JH_F32: return launch_chain_adj<float, 1, 4, 1>(ch, args, out, in, n, accumulate, first_elem, end_elem);
-    case JH_F64: return launch_chain_adj<double, 1, 2, 1>(ch, args, out, in, n, accumulate, first_elem, end_elem);
-    case JH_C32: return launch_chain_adj<float, 2, 4, 1>(ch, args, out, in, n * 2, accumulate, first_elem * 2, end_elem * 2);
-    case JH_C64: return launch_chain_adj<double, 2, 2, 1>(ch, args, out, in, n * 2, accumulate, first_elem * 2, end_elem * 2);
-    }
-    return jh_fail(JH_ERR_INVALID, "chain_launch_normal: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "chain_launch_normal", [&](auto t) {
+        using T = decltype(t);
+        return launch_chain_adj<typename T::S, T::E, T::NS, 1>(ch, args, out, in, n * T::E, accumulate, first_elem * T::E, end_elem * T::E);
+    });
 }
 }  // namespace jhb

@@ -18,12 +18,9 @@ int chain_launch_step(const jh_chain *ch, const ChainArgs &ca, void *u, const vo
     st.beta = beta;
     st.normsq = normsq;
     st.defer = defer;
-    switch (op->dtype) {
-    case JH_F32: return launch_chain_adj<float, 1, 4, 2>(ch, ca, w, v, n, 0, lo, hi, &st);
-    case JH_F64: return launch_chain_adj<double, 1, 2, 2>(ch, ca, w, v, n, 0, lo, hi, &st);
-    case JH_C32: return launch_chain_adj<float, 2, 4, 2>(ch, ca, w, v, n * 2, 0, lo * 2, hi * 2, &st);
-    case JH_C64: return launch_chain_adj<double, 2, 2, 2>(ch, ca, w, v, n * 2, 0, lo * 2, hi * 2, &st);
-    }
-    return jh_fail(JH_ERR_INVALID, "chain_launch_step: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "chain_launch_step", [&](auto t) {
+        using T = decltype(t);
+        return launch_chain_adj<typename T::S, T::E, T::NS, 2>(ch, ca, w, v, n * T::E, 0, lo * T::E, hi * T::E, &st);
+    });
 }
 }  // namespace jhb

@@ -639,12 +639,38 @@ int finish_normsq(int64_t nparts, double *normsq, bool defer = false, int privat
     return JH_OK;
 }
 
+// the fused forward update's instantiations: 256 lanes x (4 | 1) packs, MX: rows of several kinds or off the pack grid, WD: a Float64 scalar on
+// 32-bit elements, NTV: nontemporal accesses
+template <typename S, int E, int NS> struct FwdUpdatePicker {
+    using Kernel = decltype(&k_tall_diag_fwd_update<S, E, NS, 1, 256>);
+    int U;
+    bool mixed, wide, nt;
+    Picked<Kernel> got;
+    template <int UU, bool MX, bool WD, bool NTV> bool row()
+    {
+        if constexpr (!WD || sizeof(S) == 4)
+            if (U == UU && mixed == MX && wide == WD && nt == NTV) {
+                got = {&k_tall_diag_fwd_update<S, E, NS, UU, 256, MX, WD, NTV>, 256, UU, 0};
+                return true;
+            }
+        return false;
+    }
+    Picked<Kernel> pick()
+    {
+        // rows off the 16-byte grid: temporal accesses (jh_tall.hip: launch_tall_fwd_mixed), one pack per lane
+        (void)(row<4, true, false, false>() || row<1, true, false, false>() ||
+               // (a wide scalar: Float32 elements only, beta == 0 -- checked by the caller; one instantiation per tiling)
+               row<4, true, true, true>() || row<1, true, true, true>() || row<4, false, true, true>() || row<1, false, true, true>() ||
+               row<4, true, false, true>() || row<1, true, false, true>() || row<4, false, false, true>() || row<1, false, false, true>());
+        return got;
+    }
+};
+
 template <typename S, int E, int NS>
 int launch_fwd_update(const jh_blockop *op, void *d, const void *m, int64_t n_scalars, double alpha, double beta, double *normsq, bool wide = false)
 {
     jh_context &c = jh_ctx();
-    const S *a_base = op->diag_strided ? (const S *)op->blocks[0].coeff : nullptr;
-    const int64_t a_stride = op->diag_stride_elems * E;
+    const DiagBase<S> a = diag_base<S, E>(op);
     const int64_t nvec = (n_scalars + NS - 1) / NS;
     // three streams per row (a, d in, d out).  Late round 4: one pack per lane, two rows per workgroup, COLUMN bands of 32 tiles (k_tall_diag_fwd's
     // walk: 128 KiB of a row group, then the same tiles of the next, ...) -- against round 1's 256 x 4 packs x 4 rows sequential: beta = 0 (the pass of
@@ -677,6 +703,11 @@ int launch_fwd_update(const jh_blockop *op, void *d, const void *m, int64_t n_sc
     int64_t gy = (op->nrow + G - 1) / G;
     while (gx * gy * wg >= ((int64_t)1 << 32) && G < op->nrow) { G *= 2; gy = (op->nrow + G - 1) / G; }   // HIP: grid x block < 2^32 threads
     JH_REQUIRE(gx * gy * wg < ((int64_t)1 << 32), "fused forward update: grid of %lld workgroups is too large", (long long)(gx * gy));
+    const bool off_grid = packs_unaligned(op, (size_t)n_scalars * sizeof(S), d, m);
+    const bool wide_scalar = sizeof(S) == 4 && wide;
+    const bool temporal = off_grid && !wide_scalar && (c.ua_nt == 0 || c.ua_nt < 0);
+    const auto k = FwdUpdatePicker<S, E, NS>{U, mixed, wide_scalar, !temporal, {}}.pick();
+    JH_REQUIRE(k.k && k.blk == wg && k.u == U, "fused forward update: no kernel of %d x %d packs", wg, U);   // (gx is sized for wg x U)
     JH_TRY(jh_ensure_partials(gx * gy));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (trial >= 0) {
@@ -684,34 +715,8 @@ int launch_fwd_update(const jh_blockop *op, void *d, const void *m, int64_t n_sc
         JH_CHECK_HIP(hipEventCreate(&e1));
         JH_CHECK_HIP(hipEventRecord(e0, c.stream));
     }
-#define JH_LAUNCH_WN(BLK, UU, MX, WD, NTV)                                                                             \
-    hipLaunchKernelGGL((k_tall_diag_fwd_update<S, E, NS, UU, BLK, MX, WD, NTV>), dim3((unsigned)(gx * gy)), dim3(BLK), 0, c.stream, \
-                       op->dev_blocks, op->nrow, G, a_base, a_stride, (const S *)m, (S *)d, n_scalars, (unsigned)gx,   \
-                       (unsigned)gy, walk, (S)alpha, (S)beta, c.part_dev, alpha)
-#define JH_LAUNCH_W(BLK, UU, MX, WD) JH_LAUNCH_WN(BLK, UU, MX, WD, true)
-    // rows off the 16-byte grid: temporal accesses (jh_tall.hip: launch_tall_fwd_mixed), one pack per lane
-    const bool off_grid = packs_unaligned(op, (size_t)n_scalars * sizeof(S), d, m);
-    if (off_grid && !(sizeof(S) == 4 && wide) && (c.ua_nt == 0 || c.ua_nt < 0)) {
-        if (U == 4) JH_LAUNCH_WN(256, 4, true, false, false); else JH_LAUNCH_WN(256, 1, true, false, false);
-    } else
-    // (a wide scalar: Float32 elements only, beta == 0 -- checked by the caller; one instantiation per tiling)
-    if constexpr (sizeof(S) == 4) {
-        if (wide) {
-            if (mixed && U == 4) JH_LAUNCH_W(256, 4, true, true);
-            else if (mixed) JH_LAUNCH_W(256, 1, true, true);
-            else if (U == 4) JH_LAUNCH_W(256, 4, false, true);
-            else JH_LAUNCH_W(256, 1, false, true);
-        }
-    }
-    if (!(sizeof(S) == 4 && wide)) {
-        if (off_grid && (c.ua_nt == 0 || c.ua_nt < 0)) { /* launched above */ }
-        else if (mixed && U == 4) JH_LAUNCH_W(256, 4, true, false);
-        else if (mixed) JH_LAUNCH_W(256, 1, true, false);
-        else if (U == 4) JH_LAUNCH_W(256, 4, false, false);
-        else JH_LAUNCH_W(256, 1, false, false);
-    }
-#undef JH_LAUNCH_W
-#undef JH_LAUNCH_WN
+    hipLaunchKernelGGL(k.k, dim3((unsigned)(gx * gy)), dim3(k.blk), 0, c.stream, op->dev_blocks, op->nrow, G, a.base, a.stride, (const S *)m, (S *)d,
+                       n_scalars, (unsigned)gx, (unsigned)gy, walk, (S)alpha, (S)beta, c.part_dev, alpha);
     JH_CHECK_HIP(hipGetLastError());
     if (trial >= 0) JH_CHECK_HIP(hipEventRecord(e1, c.stream));
     const int st = finish_normsq(gx * gy, normsq);          // synchronises (normsq != NULL on a trial)
@@ -728,13 +733,35 @@ int launch_fwd_update(const jh_blockop *op, void *d, const void *m, int64_t n_sc
     return st;
 }
 
+// the fused adjoint update's instantiations: workgroup x packs per lane x rows in flight, WD: a Float64 in_scale on 32-bit elements
+template <typename S, int E, int NS> struct AdjUpdatePicker {
+    using Kernel = decltype(&k_tall_diag_adj_update<S, E, NS, 1, 4, 256>);
+    int wg, U;
+    bool wide;
+    Picked<Kernel> got;
+    template <int BLK, int UU, int DD, bool WD> bool row()
+    {
+        if constexpr (!WD || sizeof(S) == 4)
+            if (wg == BLK && U == UU && wide == WD) {
+                got = {&k_tall_diag_adj_update<S, E, NS, UU, DD, BLK, WD>, BLK, UU, DD};
+                return true;
+            }
+        return false;
+    }
+    Picked<Kernel> pick()
+    {
+        (void)(row<512, 4, 4, true>() || row<256, 4, 2, true>() || row<256, 2, 4, true>() || row<256, 1, 4, true>() ||
+               row<512, 4, 4, false>() || row<256, 4, 2, false>() || row<256, 2, 4, false>() || row<256, 1, 4, false>());
+        return got;
+    }
+};
+
 template <typename S, int E, int NS>
 int launch_adj_update(const jh_blockop *op, void *out, const void *in, int64_t n_scalars, double alpha, double beta, double gamma,
                       double *normsq, bool wide = false)
 {
     jh_context &c = jh_ctx();
-    const S *a_base = op->diag_strided ? (const S *)op->blocks[0].coeff : nullptr;
-    const int64_t a_stride = op->diag_stride_elems * E;
+    const DiagBase<S> a = diag_base<S, E>(op);
     const int64_t nvec = (n_scalars + NS - 1) / NS;
     const int direct = op->nrow == 1 ? 1 : 0;
     {   // many rows of small blocks: the row sum through the split walk of the plain adjoint, then out = (alpha*gamma)*t + beta*out
@@ -759,25 +786,10 @@ int launch_adj_update(const jh_blockop *op, void *out, const void *in, int64_t n
     if (nvec >= ((int64_t)1 << 22)) wg = 512;
     const int64_t gx = (nvec + (int64_t)wg * U - 1) / ((int64_t)wg * U);
     JH_TRY(jh_ensure_partials(gx));
-#define JH_LAUNCH_W(BLK, UU, DD, WD)                                                                                   \
-    hipLaunchKernelGGL((k_tall_diag_adj_update<S, E, NS, UU, DD, BLK, WD>), dim3((unsigned)gx), dim3(BLK), 0, c.stream, \
-                       op->dev_blocks, op->nrow, a_base, a_stride, (S *)out, (const S *)in, n_scalars, direct, (S)alpha, \
-                       (S)beta, (S)gamma, c.part_dev, gamma)
-    if constexpr (sizeof(S) == 4) {
-        if (wide) {
-            if (wg == 512) JH_LAUNCH_W(512, 4, 4, true);
-            else if (U == 4) JH_LAUNCH_W(256, 4, 2, true);
-            else if (U == 2) JH_LAUNCH_W(256, 2, 4, true);
-            else JH_LAUNCH_W(256, 1, 4, true);
-        }
-    }
-    if (!(sizeof(S) == 4 && wide)) {
-        if (wg == 512) JH_LAUNCH_W(512, 4, 4, false);
-        else if (U == 4) JH_LAUNCH_W(256, 4, 2, false);
-        else if (U == 2) JH_LAUNCH_W(256, 2, 4, false);
-        else JH_LAUNCH_W(256, 1, 4, false);
-    }
-#undef JH_LAUNCH_W
+    const auto k = AdjUpdatePicker<S, E, NS>{wg, U, sizeof(S) == 4 && wide, {}}.pick();
+    JH_REQUIRE(k.k && k.blk == wg && k.u == U, "fused adjoint update: no kernel of %d x %d packs", wg, U);   // (gx is sized for wg x U)
+    hipLaunchKernelGGL(k.k, dim3((unsigned)gx), dim3(k.blk), 0, c.stream, op->dev_blocks, op->nrow, a.base, a.stride, (S *)out, (const S *)in, n_scalars,
+                       direct, (S)alpha, (S)beta, (S)gamma, c.part_dev, gamma);
     JH_CHECK_HIP(hipGetLastError());
     return finish_normsq(gx, normsq);
 }
@@ -810,6 +822,60 @@ static StepShape pick_step_shape(const jh_blockop *op, int64_t nvec, bool comple
     return {wg, U, D};
 }
 
+// the plain walk's instantiations, first match of (workgroup, packs per lane, rows in flight, rows of several kinds or off the pack grid); NTV: nontemporal accesses
+template <typename S, int E, int NS> struct BidiagPicker {
+    using Kernel = decltype(&k_tall_diag_bidiag<S, E, NS, 1, 4, 256>);
+    StepShape want;
+    bool mixed;
+    Picked<Kernel> got;
+    template <int BLK, int UU, int DD, bool MIX = false, bool NTV = true> bool row()
+    {
+        if constexpr (!(E == 2 && sizeof(S) == 4 && BLK == 1024 && UU == 4 && DD == 1))   // (ComplexF32 1024 x 4 x 1 spills: pick_step_shape never asks for it)
+            if (want.wg == BLK && want.U == UU && want.D == DD && mixed == MIX) {
+                got = {&k_tall_diag_bidiag<S, E, NS, UU, DD, BLK, MIX, NTV>, BLK, UU, DD};
+                return true;
+            }
+        return false;
+    }
+    Picked<Kernel> pick(bool fits_cache, bool off_grid_temporal)
+    {
+        (void)(
+            // operators whose pass fits the Infinity Cache (jh_stream_nt: knob nt) run the three shapes small blocks select with TEMPORAL loads / stores
+            (fits_cache && (row<256, 1, 4, false, false>() || row<256, 2, 2, false, false>() || row<256, 4, 1, false, false>())) ||
+            row<256, 1, 4>() || row<256, 2, 2>() || row<256, 4, 1>() || row<256, 4, 2>() || row<256, 1, 8>() ||
+            row<512, 1, 4>() || row<512, 2, 2>() || row<512, 4, 1>() || row<512, 4, 2>() || row<512, 1, 8>() ||
+            row<1024, 1, 4>() || row<1024, 2, 2>() || row<1024, 4, 1>() ||      // 1024 x 4 x 2 would need > 128 VGPRs per lane
+            // rows off the 16-byte grid: temporal accesses (jh_tall.hip: launch_tall_fwd_mixed)
+            (off_grid_temporal && (row<512, 1, 4, true, false>() || row<256, 2, 2, true, false>() || row<256, 4, 1, true, false>() || row<256, 1, 4, true, false>())) ||
+            row<512, 1, 4, true>() || row<256, 2, 2, true>() || row<256, 4, 1, true>() || row<256, 1, 4, true>());
+        return got;
+    }
+};
+
+// the chained walk's instantiations: one pack per lane, (workgroup, rows per chunk, rows of several kinds)
+template <typename S, int E, int NS> struct BidiagChainPicker {
+    using Kernel = decltype(&k_tall_diag_bidiag_chain<S, E, NS, 1, 8, 256>);
+    int cb, CD;
+    bool mixed;
+    Picked<Kernel> got;
+    template <int BLK, int CDD, bool MIX> bool row()
+    {
+        if (cb == BLK && CD == CDD && mixed == MIX) {
+            got = {&k_tall_diag_bidiag_chain<S, E, NS, 1, CDD, BLK, MIX>, BLK, 1, CDD};
+            return true;
+        }
+        return false;
+    }
+    Picked<Kernel> pick()
+    {
+        (void)(row<1024, 8, true>() || row<512, 8, true>() || row<256, 8, true>() ||
+               row<256, 32, false>() ||
+               row<512, 16, false>() || row<256, 16, false>() ||
+               row<1024, 8, false>() || row<512, 8, false>() || row<256, 8, false>());
+        return got;
+    }
+};
+
 template <typename S, int E, int NS>
 int launch_bidiag(const jh_blockop *op, void *u, const void *v, void *w, int64_t n_scalars, double alpha, double beta, double *normsq,
                   int64_t s_begin = 0, int64_t s_end = -1, bool defer = false)
@@ -817,8 +883,7 @@ int launch_bidiag(const jh_blockop *op, void *u, const void *v, void *w, int64_t
     if (s_end < 0) s_end = n_scalars;
     if (s_end <= s_begin) { if (normsq) *normsq = 0.0; return JH_OK; }
     jh_context &c = jh_ctx();
-    const S *a_base = op->diag_strided ? (const S *)op->blocks[0].coeff : nullptr;
-    const int64_t a_stride = op->diag_stride_elems * E;
+    const DiagBase<S> a = diag_base<S, E>(op);
     const int64_t nvec = n_scalars / NS;
     const int direct = op->nrow == 1 ? 1 : 0;
     const bool unaligned = packs_unaligned(op, (size_t)n_scalars * sizeof(S), u, v, w);   // (whole-vector calls only: jh_blockop_bidiag_step)
@@ -909,6 +974,8 @@ int launch_bidiag(const jh_blockop *op, void *u, const void *v, void *w, int64_t
         return st;
     };
     if (mode == 2) {
+        const auto k = BidiagChainPicker<S, E, NS>{cb, CD, mixed, {}}.pick();
+        JH_REQUIRE(k.k && k.blk == cb && k.depth == CD, "chained one-pass step: no kernel of %d lanes x %d rows per chunk", cb, CD);   // (ntiles, nchunks are sized for cb x CD)
         if (c.chain_sync_cap < 2 + ntiles) {
             if (c.chain_sync) { JH_CHECK_HIP(hipStreamSynchronize(c.stream)); JH_CHECK_HIP(hipFree(c.chain_sync)); c.chain_sync = nullptr; c.chain_sync_cap = 0; }
             int64_t cap = 4096;
@@ -925,27 +992,9 @@ int launch_bidiag(const jh_blockop *op, void *u, const void *v, void *w, int64_t
         // column bands of the chained walk (knob step_band: -1 the default below, 0 none = tiles fastest over the whole row, k tiles per band)
         int64_t cband = c.step_band >= 0 ? c.step_band : 0;
         if (cband >= ntiles) cband = 0;
-#define JH_CHAIN(BLK, MIX) JH_CHAIN_D(BLK, MIX, 8)
-#define JH_CHAIN_D(BLK, MIX, CDD)                                                                                         \
-    hipLaunchKernelGGL((k_tall_diag_bidiag_chain<S, E, NS, 1, CDD, BLK, MIX>), dim3((unsigned)(ntiles * nchunks)), dim3(BLK), 0, c.stream, \
-                       op->dev_blocks, op->nrow, a_base, a_stride, (S *)u, (const S *)v, (S *)w, n_scalars, (S)alpha, (S)beta,   \
-                       c.part_dev, s_begin, s_end, (unsigned)ntiles, (unsigned)nchunks, c.chain_sync, (S *)wpart, err, (unsigned)cband)
-        if (mixed) {
-            if (cb == 1024) JH_CHAIN(1024, true);
-            else if (cb == 512) JH_CHAIN(512, true);
-            else JH_CHAIN(256, true);
-        } else if (CD == 32) {
-            JH_CHAIN_D(256, false, 32);
-        } else if (CD == 16) {
-            if (cb == 512) JH_CHAIN_D(512, false, 16);
-            else JH_CHAIN_D(256, false, 16);
-        } else {
-            if (cb == 1024) JH_CHAIN(1024, false);
-            else if (cb == 512) JH_CHAIN(512, false);
-            else JH_CHAIN(256, false);
-        }
-#undef JH_CHAIN
-#undef JH_CHAIN_D
+        hipLaunchKernelGGL(k.k,dim3((unsigned)(ntiles * nchunks)), dim3(k.blk), 0, c.stream, op->dev_blocks, op->nrow, a.base, a.stride, (S *)u,
+                           (const S *)v, (S *)w, n_scalars, (S)alpha, (S)beta, c.part_dev, s_begin, s_end, (unsigned)ntiles, (unsigned)nchunks,
+                           c.chain_sync, (S *)wpart, err, (unsigned)cband);
         JH_CHECK_HIP(hipGetLastError());
         c.last_step_chain = nchunks;
         c.last_adj_parts = 1;
@@ -955,55 +1004,34 @@ int launch_bidiag(const jh_blockop *op, void *u, const void *v, void *w, int64_t
         return trial_done(st_);
     }
     c.last_step_chain = 0;
-#define JH_LAUNCH(BLK, UU, DD) JH_LAUNCH_M(BLK, UU, DD, false)
-#define JH_LAUNCH_T(BLK, UU, DD) JH_LAUNCH_N(BLK, UU, DD, false, false)
-#define JH_LAUNCH_M(BLK, UU, DD, MIX) JH_LAUNCH_N(BLK, UU, DD, MIX, true)
-#define JH_LAUNCH_N(BLK, UU, DD, MIX, NTV)                                                                              \
-    if constexpr (!(E == 2 && sizeof(S) == 4 && BLK == 1024 && UU == 4 && DD == 1))                                      \
-    if (wg == BLK && U == UU && D == DD && mixed == MIX) {                                                              \
-        double total = 0.0;                                                                                              \
-        const bool several = rows_per_launch < op->nrow && normsq != nullptr;   /* one read-back for all the launches */     \
-        if (several) JH_CHECK_HIP(hipMemsetAsync(c.red_dev + 9, 0, sizeof(double), c.stream));                           \
-        for (int64_t r0 = 0; r0 < op->nrow; r0 += rows_per_launch) {                                                     \
-            const int64_t r1 = r0 + rows_per_launch < op->nrow ? r0 + rows_per_launch : op->nrow;                          \
-            hipLaunchKernelGGL((k_tall_diag_bidiag<S, E, NS, UU, DD, BLK, MIX, NTV>), dim3((unsigned)gx, (unsigned)parts), dim3(BLK), 0, \
-                               c.stream,                                                                                 \
-                               op->dev_blocks, op->nrow, a_base, a_stride, (S *)u, (const S *)v, (S *)w, n_scalars,      \
-                               direct, (S)alpha, (S)beta, c.part_dev, s_begin, s_end, r0, r1, r0 > 0 ? 1 : 0,              \
-                               rows_per_part, (S *)slabs, part_stride, remap, c.step_coef_dev, c.step_done_dev);        \
-            JH_CHECK_HIP(hipGetLastError());                                                                             \
-            if (parts > 1) JH_TRY(jhb::fold_parts(op->dtype, slabs, part_stride, parts, w, s_begin, s_end));              \
-            double part = 0.0;                                                                                           \
-            c.last_step_parts = gx * parts;                                                                              \
-            if (c.step_coef_dev && c.step_skip_fold) return trial_done(JH_OK);   /* the caller folds part_dev itself */    \
-            const int st_ = finish_normsq(gx * parts, normsq ? &part : nullptr, defer, several ? 9 : -1);                \
-            if (st_ != JH_OK) return trial_done(st_);                                                                    \
-            total += part;                                                                                               \
-        }                                                                                                                \
-        if (several) {                                                                                                   \
-            JH_CHECK_HIP(hipMemcpyAsync(c.red_host + 7, c.red_dev + 9, sizeof(double), hipMemcpyDeviceToHost, c.stream)); \
-            JH_CHECK_HIP(hipStreamSynchronize(c.stream));                                                                \
-            total = c.red_host[7];                                                                                       \
-        }                                                                                                                \
-        if (normsq) *normsq = total;                                                                                     \
-        return trial_done(JH_OK);                                                                                        \
+    const bool fits_cache = !mixed && wg == 256 && !jh_stream_nt(2.0 * (double)op->nrow * (double)n_scalars * sizeof(S));
+    const auto k = BidiagPicker<S, E, NS>{shape, mixed, {}}.pick(fits_cache, unaligned && c.ua_nt <= 0);
+    if (!k.k) return jh_fail(JH_ERR_INVALID, "fused bidiagonalisation step: shape %d x %d x %d is not instantiated", wg, U, D);
+    JH_REQUIRE(k.blk == wg && k.u == U, "fused bidiagonalisation step: picked %d x %d for a grid of %d x %d", k.blk, k.u, wg, U);   // (gx is sized for wg x U)
+    double total = 0.0;
+    const bool several = rows_per_launch < op->nrow && normsq != nullptr;   // one read-back for all the launches
+    if (several) JH_CHECK_HIP(hipMemsetAsync(c.red_dev + 9, 0, sizeof(double), c.stream));
+    for (int64_t r0 = 0; r0 < op->nrow; r0 += rows_per_launch) {
+        const int64_t r1 = r0 + rows_per_launch < op->nrow ? r0 + rows_per_launch : op->nrow;
+        hipLaunchKernelGGL(k.k, dim3((unsigned)gx, (unsigned)parts), dim3(k.blk), 0, c.stream, op->dev_blocks, op->nrow, a.base, a.stride, (S *)u,
+                           (const S *)v, (S *)w, n_scalars, direct, (S)alpha, (S)beta, c.part_dev, s_begin, s_end, r0, r1, r0 > 0 ? 1 : 0,
+                           rows_per_part, (S *)slabs, part_stride, remap, c.step_coef_dev, c.step_done_dev);
+        JH_CHECK_HIP(hipGetLastError());
+        if (parts > 1) JH_TRY(jhb::fold_parts(op->dtype, slabs, part_stride, parts, w, s_begin, s_end));
+        double part = 0.0;
+        c.last_step_parts = gx * parts;
+        if (c.step_coef_dev && c.step_skip_fold) return trial_done(JH_OK);   // the caller folds part_dev itself
+        const int st_ = finish_normsq(gx * parts, normsq ? &part : nullptr, defer, several ? 9 : -1);
+        if (st_ != JH_OK) return trial_done(st_);
+        total += part;
     }
-    // operators whose pass fits the Infinity Cache (jh_stream_nt: knob nt) run the three shapes small blocks select with TEMPORAL loads / stores
-    if (!mixed && wg == 256 && !jh_stream_nt(2.0 * (double)op->nrow * (double)n_scalars * sizeof(S))) {
-        JH_LAUNCH_T(256, 1, 4) JH_LAUNCH_T(256, 2, 2) JH_LAUNCH_T(256, 4, 1)
+    if (several) {
+        JH_CHECK_HIP(hipMemcpyAsync(c.red_host + 7, c.red_dev + 9, sizeof(double), hipMemcpyDeviceToHost, c.stream));
+        JH_CHECK_HIP(hipStreamSynchronize(c.stream));
+        total = c.red_host[7];
     }
-    JH_LAUNCH(256, 1, 4) JH_LAUNCH(256, 2, 2) JH_LAUNCH(256, 4, 1) JH_LAUNCH(256, 4, 2) JH_LAUNCH(256, 1, 8)
-    JH_LAUNCH(512, 1, 4) JH_LAUNCH(512, 2, 2) JH_LAUNCH(512, 4, 1) JH_LAUNCH(512, 4, 2) JH_LAUNCH(512, 1, 8)
-    JH_LAUNCH(1024, 1, 4) JH_LAUNCH(1024, 2, 2) JH_LAUNCH(1024, 4, 1)      // 1024 x 4 x 2 would need > 128 VGPRs per lane
-    if (unaligned && c.ua_nt <= 0) {                                       // rows off the 16-byte grid: temporal accesses (jh_tall.hip: launch_tall_fwd_mixed)
-        JH_LAUNCH_N(512, 1, 4, true, false) JH_LAUNCH_N(256, 2, 2, true, false) JH_LAUNCH_N(256, 4, 1, true, false) JH_LAUNCH_N(256, 1, 4, true, false)
-    }
-    JH_LAUNCH_M(512, 1, 4, true) JH_LAUNCH_M(256, 2, 2, true) JH_LAUNCH_M(256, 4, 1, true) JH_LAUNCH_M(256, 1, 4, true)
-#undef JH_LAUNCH
-#undef JH_LAUNCH_T
-#undef JH_LAUNCH_M
-#undef JH_LAUNCH_N
-    return jh_fail(JH_ERR_INVALID, "fused bidiagonalisation step: shape %d x %d x %d is not instantiated", wg, U, D);
+    if (normsq) *normsq = total;
+    return trial_done(JH_OK);
 }
 
 
@@ -1041,13 +1069,10 @@ int jh_blockop_bidiag_step(const jh_blockop *op, jh_bvec *u, const jh_bvec *v, j
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_blockop_bidiag_step: needs a tall operator of >= 2 equal elementwise rows or an N x (2 .. 4) grid of equal elementwise blocks");
     }
     const int64_t n = op->row_len[0];
-    switch (op->dtype) {
-    case JH_F32: return launch_bidiag<float, 1, 4>(op, u->data, v->data, w->data, n, alpha, beta, normsq);
-    case JH_F64: return launch_bidiag<double, 1, 2>(op, u->data, v->data, w->data, n, alpha, beta, normsq);
-    case JH_C32: return launch_bidiag<float, 2, 4>(op, u->data, v->data, w->data, 2 * n, alpha, beta, normsq);
-    case JH_C64: return launch_bidiag<double, 2, 2>(op, u->data, v->data, w->data, 2 * n, alpha, beta, normsq);
-    }
-    return jh_fail(JH_ERR_INVALID, "jh_blockop_bidiag_step: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "jh_blockop_bidiag_step", [&](auto t) {
+        using T = decltype(t);
+        return launch_bidiag<typename T::S, T::E, T::NS>(op, u->data, v->data, w->data, n * T::E, alpha, beta, normsq);
+    });
 }
 
 int jh_blockop_bidiag_step_range(const jh_blockop *op, jh_bvec *u, const jh_bvec *v, jh_bvec *w, double alpha, double beta,
@@ -1078,13 +1103,10 @@ int jh_blockop_bidiag_step_range(const jh_blockop *op, jh_bvec *u, const jh_bvec
     JH_REQUIRE((first_elem * es) % 16 == 0 && ((count * es) % 16 == 0 || first_elem + count == v->length),
                "jh_blockop_bidiag_step_range: chunk boundaries must be 16-byte aligned (the last chunk may end with the vector)");
     const int64_t n = op->row_len[0], lo = first_elem, hi = first_elem + count;
-    switch (op->dtype) {
-    case JH_F32: return launch_bidiag<float, 1, 4>(op, u->data, v->data, w->data, n, alpha, beta, normsq, lo, hi, true);
-    case JH_F64: return launch_bidiag<double, 1, 2>(op, u->data, v->data, w->data, n, alpha, beta, normsq, lo, hi, true);
-    case JH_C32: return launch_bidiag<float, 2, 4>(op, u->data, v->data, w->data, 2 * n, alpha, beta, normsq, 2 * lo, 2 * hi, true);
-    case JH_C64: return launch_bidiag<double, 2, 2>(op, u->data, v->data, w->data, 2 * n, alpha, beta, normsq, 2 * lo, 2 * hi, true);
-    }
-    return jh_fail(JH_ERR_INVALID, "jh_blockop_bidiag_step_range: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "jh_blockop_bidiag_step_range", [&](auto t) {
+        using T = decltype(t);
+        return launch_bidiag<typename T::S, T::E, T::NS>(op, u->data, v->data, w->data, n * T::E, alpha, beta, normsq, lo * T::E, hi * T::E, true);
+    });
 }
 
 int jh_normsq_reset(void)
@@ -1115,13 +1137,10 @@ int jh_blockop_mul_axpby(const jh_blockop *op, jh_bvec *d, const jh_bvec *m, dou
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_blockop_mul_axpby: needs a tall operator of equal elementwise rows; "
                                            "use jh_blockop_mul into a temporary, jh_lincomb and jh_norm instead");
     const int64_t n = op->row_len[0];
-    switch (op->dtype) {
-    case JH_F32: return launch_fwd_update<float, 1, 4>(op, d->data, m->data, n, alpha, beta, normsq);
-    case JH_F64: return launch_fwd_update<double, 1, 2>(op, d->data, m->data, n, alpha, beta, normsq);
-    case JH_C32: return launch_fwd_update<float, 2, 4>(op, d->data, m->data, 2 * n, alpha, beta, normsq);
-    case JH_C64: return launch_fwd_update<double, 2, 2>(op, d->data, m->data, 2 * n, alpha, beta, normsq);
-    }
-    return jh_fail(JH_ERR_INVALID, "jh_blockop_mul_axpby: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "jh_blockop_mul_axpby", [&](auto t) {
+        using T = decltype(t);
+        return launch_fwd_update<typename T::S, T::E, T::NS>(op, d->data, m->data, n * T::E, alpha, beta, normsq);
+    });
 }
 
 int jh_blockop_mul_adj_axpby(const jh_blockop *op, jh_bvec *m, const jh_bvec *d, double alpha, double beta, double in_scale,
@@ -1133,13 +1152,10 @@ int jh_blockop_mul_adj_axpby(const jh_blockop *op, jh_bvec *m, const jh_bvec *d,
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_blockop_mul_adj_axpby: needs a tall all-DIAG operator with equal blocks; "
                                            "use jh_blockop_mul_adj into a temporary, jh_lincomb and jh_norm instead");
     const int64_t n = op->row_len[0];
-    switch (op->dtype) {
-    case JH_F32: return launch_adj_update<float, 1, 4>(op, m->data, d->data, n, alpha, beta, in_scale, normsq);
-    case JH_F64: return launch_adj_update<double, 1, 2>(op, m->data, d->data, n, alpha, beta, in_scale, normsq);
-    case JH_C32: return launch_adj_update<float, 2, 4>(op, m->data, d->data, 2 * n, alpha, beta, in_scale, normsq);
-    case JH_C64: return launch_adj_update<double, 2, 2>(op, m->data, d->data, 2 * n, alpha, beta, in_scale, normsq);
-    }
-    return jh_fail(JH_ERR_INVALID, "jh_blockop_mul_adj_axpby: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "jh_blockop_mul_adj_axpby", [&](auto t) {
+        using T = decltype(t);
+        return launch_adj_update<typename T::S, T::E, T::NS>(op, m->data, d->data, n * T::E, alpha, beta, in_scale, normsq);
+    });
 }
 
 // (a * A) m and (a * A)' d = A'(conj(a) d) of the scalar-times-operator chain (src/Jets.jl:1159-1164) in one pass each, for a REAL scalar of
@@ -1156,13 +1172,11 @@ int jh_blockop_mul_scaled(const jh_blockop *op, jh_bvec *d, const jh_bvec *m, do
         return jh_fail(JH_ERR_UNSUPPORTED, "jh_blockop_mul_scaled: needs a tall operator of equal elementwise rows");
     const int64_t n = op->row_len[0];
     const bool wide = (a_flags & JH_SCALAR_WIDE) != 0;
-    switch (op->dtype) {
-    case JH_F32: return launch_fwd_update<float, 1, 4>(op, d->data, m->data, n, a, 0.0, nullptr, wide);
-    case JH_F64: return launch_fwd_update<double, 1, 2>(op, d->data, m->data, n, a, 0.0, nullptr);
-    case JH_C32: return launch_fwd_update<float, 2, 4>(op, d->data, m->data, 2 * n, a, 0.0, nullptr, wide);
-    case JH_C64: return launch_fwd_update<double, 2, 2>(op, d->data, m->data, 2 * n, a, 0.0, nullptr);
-    }
-    return jh_fail(JH_ERR_INVALID, "jh_blockop_mul_scaled: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "jh_blockop_mul_scaled", [&](auto t) {
+        using T = decltype(t);
+        if constexpr (sizeof(typename T::S) == 4) return launch_fwd_update<typename T::S, T::E, T::NS>(op, d->data, m->data, n * T::E, a, 0.0, nullptr, wide);
+        else return launch_fwd_update<typename T::S, T::E, T::NS>(op, d->data, m->data, n * T::E, a, 0.0, nullptr);
+    });
 }
 
 int jh_blockop_mul_adj_scaled(const jh_blockop *op, jh_bvec *m, const jh_bvec *d, double a, int a_flags)
@@ -1187,13 +1201,11 @@ int jh_blockop_mul_adj_scaled(const jh_blockop *op, jh_bvec *m, const jh_bvec *d
     }
     const int64_t n = op->row_len[0];
     const bool wide = (a_flags & JH_SCALAR_WIDE) != 0;
-    switch (op->dtype) {
-    case JH_F32: return launch_adj_update<float, 1, 4>(op, m->data, d->data, n, 1.0, 0.0, a, nullptr, wide);
-    case JH_F64: return launch_adj_update<double, 1, 2>(op, m->data, d->data, n, 1.0, 0.0, a, nullptr);
-    case JH_C32: return launch_adj_update<float, 2, 4>(op, m->data, d->data, 2 * n, 1.0, 0.0, a, nullptr, wide);
-    case JH_C64: return launch_adj_update<double, 2, 2>(op, m->data, d->data, 2 * n, 1.0, 0.0, a, nullptr);
-    }
-    return jh_fail(JH_ERR_INVALID, "jh_blockop_mul_adj_scaled: unknown dtype %d", op->dtype);
+    return jh_by_dtype(op->dtype, "jh_blockop_mul_adj_scaled", [&](auto t) {
+        using T = decltype(t);
+        if constexpr (sizeof(typename T::S) == 4) return launch_adj_update<typename T::S, T::E, T::NS>(op, m->data, d->data, n * T::E, 1.0, 0.0, a, nullptr, wide);
+        else return launch_adj_update<typename T::S, T::E, T::NS>(op, m->data, d->data, n * T::E, 1.0, 0.0, a, nullptr);
+    });
 }
 
 }  // extern "C"

@@ -387,6 +387,33 @@ static int sum_prepare(int nterms, const jh_blockop *const *ops, const double *s
     return JH_OK;
 }
 
+// the fused sum forward's instantiations: 256 lanes, one row in flight, accumulators for up to 16 / 12 / 8 / 4 terms; ST: the diagonals of every term are
+// blocks of one slab at one stride, WD: a Float64 scale on 32-bit elements (promoted products, k_tall_sum_fwd)
+// (D = 2 rows in flight per workgroup were measured and lose 3-6 % in the forward: profiles/exp_r05_jetsum_rows.txt)
+template <typename S, int E, int NS> struct SumFwdPicker {
+    using Kernel = decltype(&k_tall_sum_fwd<S, E, NS, 1, 256, 16, true>);
+    int terms;
+    bool strided, wide;
+    Picked<Kernel> got;
+    template <bool ST, bool WD> bool rows()
+    {
+        if constexpr (!WD || sizeof(S) == 4)
+            if (strided == ST && wide == WD) {
+                if (terms > 12) got = {&k_tall_sum_fwd<S, E, NS, 1, 256, 16, ST, WD, 1>, 256, 1, 1};
+                else if (terms > 8) got = {&k_tall_sum_fwd<S, E, NS, 1, 256, 12, ST, WD, 1>, 256, 1, 1};
+                else if (terms > 4) got = {&k_tall_sum_fwd_few<S, E, NS, 2, 256, 8, 1, ST, WD>, 256, 2, 1};
+                else got = {&k_tall_sum_fwd_few<S, E, NS, 2, 256, 4, 1, ST, WD>, 256, 2, 1};
+                return true;
+            }
+        return false;
+    }
+    Picked<Kernel> pick()
+    {
+        (void)(rows<true, true>() || rows<false, true>() || rows<true, false>() || rows<false, false>());
+        return got;
+    }
+};
+
 template <typename S, int E, int NS>
 static int sum_fwd_launch(const SumArgs &a, bool strided, const jh_blockop *op0, void *d, const void *m, int64_t n_scalars, int accumulate, bool wide = false)
 {
@@ -405,35 +432,9 @@ static int sum_fwd_launch(const SumArgs &a, bool strided, const jh_blockop *op0,
     int64_t gy = (op0->nrow + G - 1) / G;
     while (gx * gy * BLK >= ((int64_t)1 << 32) && G < op0->nrow) { G *= 2; gy = (op0->nrow + G - 1) / G; }
     JH_REQUIRE(gx * gy * BLK < ((int64_t)1 << 32), "fused sum forward: grid too large");
-#define JH_SUM_FWD_D(UU, KM, ST, WD, DD)                                                                                                 \
-    hipLaunchKernelGGL((k_tall_sum_fwd<S, E, NS, UU, BLK, KM, ST, WD, DD>), dim3((unsigned)(gx * gy)), dim3(BLK), 0, c.stream, a, op0->nrow, G, \
-                       (const S *)m, (S *)d, n_scalars, (unsigned)gx, accumulate)
-// (D = 2 rows in flight per workgroup were measured and lose 3-6 % in the forward: profiles/exp_r05_jetsum_rows.txt)
-#define JH_SUM_FWD(UU, KM, ST, WD) JH_SUM_FWD_D(UU, KM, ST, WD, 1)
-#define JH_SUM_FWD_FEW(UU, KM, ST, WD)                                                                                                   \
-    hipLaunchKernelGGL((k_tall_sum_fwd_few<S, E, NS, UU, BLK, KM, 1, ST, WD>), dim3((unsigned)(gx * gy)), dim3(BLK), 0, c.stream, a, op0->nrow, G, \
-                       (const S *)m, (S *)d, n_scalars, (unsigned)gx, accumulate)
-#define JH_SUM_FWD_K(ST, WD)                                                                                                             \
-    do {                                                                                                                                 \
-        if (a.k > 12) JH_SUM_FWD(1, 16, ST, WD);                                                                                         \
-        else if (a.k > 8) JH_SUM_FWD(1, 12, ST, WD);                                                                                     \
-        else if (a.k > 4) JH_SUM_FWD_FEW(2, 8, ST, WD);                                                                                  \
-        else JH_SUM_FWD_FEW(2, 4, ST, WD);                                                                                               \
-    } while (0)
-    bool done = false;
-    if constexpr (sizeof(S) == 4) {
-        if (wide) {                                                         // a Float64 scale on 32-bit elements: promoted products (k_tall_sum_fwd)
-            if (strided) JH_SUM_FWD_K(true, true); else JH_SUM_FWD_K(false, true);
-            done = true;
-        }
-    }
-    if (!done) {
-        if (strided) JH_SUM_FWD_K(true, false); else JH_SUM_FWD_K(false, false);
-    }
-#undef JH_SUM_FWD_K
-#undef JH_SUM_FWD_FEW
-#undef JH_SUM_FWD
-#undef JH_SUM_FWD_D
+    const auto k = SumFwdPicker<S, E, NS>{a.k, strided, sizeof(S) == 4 && wide, {}}.pick();
+    JH_REQUIRE(k.k && k.blk == BLK && k.u == U, "fused sum forward: no kernel of %d x %d packs for %d terms", BLK, U, a.k);   // (gx is sized for BLK x U)
+    hipLaunchKernelGGL(k.k, dim3((unsigned)(gx * gy)), dim3(k.blk), 0, c.stream, a, op0->nrow, G, (const S *)m, (S *)d, n_scalars, (unsigned)gx, accumulate);
     JH_CHECK_HIP(hipGetLastError());
     return JH_OK;
 }
@@ -455,41 +456,43 @@ static int sum_adj_split(int nterms, const jh_blockop *const *ops, const double 
     return JH_OK;
 }
 
+// the fused sum adjoint's instantiations: 256 lanes x packs per lane x rows in flight, accumulators for up to 16 / 12 / 8 / 4 terms (ST, WD: SumFwdPicker)
+template <typename S, int E, int NS> struct SumAdjPicker {
+    using Kernel = decltype(&k_tall_sum_adj<S, E, NS, 1, 1, 256, 16, true>);
+    int terms;
+    bool strided, wide;
+    Picked<Kernel> got;
+    template <bool ST, bool WD> bool rows()
+    {
+        if constexpr (!WD || sizeof(S) == 4)
+            if (strided == ST && wide == WD) {
+                if (terms > 12) got = {&k_tall_sum_adj<S, E, NS, 1, 1, 256, 16, ST, WD>, 256, 1, 1};      // sixteen accumulators, one row in flight (two: +1 ... +2 %, noise level: exp_r05_jetsum_rows.txt)
+                else if (terms > 8) got = {&k_tall_sum_adj<S, E, NS, 1, 1, 256, 12, ST, WD>, 256, 1, 1};
+                else if (terms > 4) got = {&k_tall_sum_adj_few<S, E, NS, 1, 2, 256, 8, ST, WD>, 256, 1, 2};
+                else got = {&k_tall_sum_adj_few<S, E, NS, 2, 2, 256, 4, ST, WD>, 256, 2, 2};
+                return true;
+            }
+        return false;
+    }
+    Picked<Kernel> pick()
+    {
+        (void)(rows<true, true>() || rows<false, true>() || rows<true, false>() || rows<false, false>());
+        return got;
+    }
+};
+
 template <typename S, int E, int NS>
 static int sum_adj_launch(const SumArgs &a, bool strided, const jh_blockop *op0, void *m, const void *d, int64_t n_scalars, int accumulate, bool wide = false)
 {
     jh_context &c = jh_ctx();
     c.last_adj_parts = 1;
-    constexpr int BLK = 256, DEPTH = 2;
+    constexpr int BLK = 256;
     const int U = a.k > 4 ? 1 : 2;
     const int64_t nvec = (n_scalars + NS - 1) / NS;
     const int64_t gx = (nvec + (int64_t)BLK * U - 1) / ((int64_t)BLK * U);
-#define JH_SUM_ADJ_K(UU, DD, KM, ST, WD)                                                                                              \
-    hipLaunchKernelGGL((k_tall_sum_adj<S, E, NS, UU, DD, BLK, KM, ST, WD>), dim3((unsigned)gx), dim3(BLK), 0, c.stream, a, op0->nrow, (S *)m, \
-                       (const S *)d, n_scalars, accumulate)
-#define JH_SUM_ADJ_FEW(UU, DD, KM, ST, WD)                                                                                            \
-    hipLaunchKernelGGL((k_tall_sum_adj_few<S, E, NS, UU, DD, BLK, KM, ST, WD>), dim3((unsigned)gx), dim3(BLK), 0, c.stream, a, op0->nrow, (S *)m, \
-                       (const S *)d, n_scalars, accumulate)
-#define JH_SUM_ADJ_S(ST, WD)                                                                                                          \
-    do {                                                                                                                              \
-        if (a.k > 12) JH_SUM_ADJ_K(1, 1, 16, ST, WD);      /* sixteen accumulators, one row in flight (two: +1 ... +2 %, noise level: exp_r05_jetsum_rows.txt) */ \
-        else if (a.k > 8) JH_SUM_ADJ_K(1, 1, 12, ST, WD);                                                                             \
-        else if (a.k > 4) JH_SUM_ADJ_FEW(1, DEPTH, 8, ST, WD);                                                                        \
-        else JH_SUM_ADJ_FEW(2, DEPTH, 4, ST, WD);                                                                                     \
-    } while (0)
-    bool done = false;
-    if constexpr (sizeof(S) == 4) {
-        if (wide) {
-            if (strided) JH_SUM_ADJ_S(true, true); else JH_SUM_ADJ_S(false, true);
-            done = true;
-        }
-    }
-    if (!done) {
-        if (strided) JH_SUM_ADJ_S(true, false); else JH_SUM_ADJ_S(false, false);
-    }
-#undef JH_SUM_ADJ_S
-#undef JH_SUM_ADJ_FEW
-#undef JH_SUM_ADJ_K
+    const auto k = SumAdjPicker<S, E, NS>{a.k, strided, sizeof(S) == 4 && wide, {}}.pick();
+    JH_REQUIRE(k.k && k.blk == BLK && k.u == U, "fused sum adjoint: no kernel of %d x %d packs for %d terms", BLK, U, a.k);   // (gx is sized for BLK x U)
+    hipLaunchKernelGGL(k.k, dim3((unsigned)gx), dim3(k.blk), 0, c.stream, a, op0->nrow, (S *)m, (const S *)d, n_scalars, accumulate);
     JH_CHECK_HIP(hipGetLastError());
     return JH_OK;
 }
@@ -530,15 +533,11 @@ int jh_blocksum_mul_typed(int nterms, const jh_blockop *const *ops, const double
         bool wide = false, strided = false;
         JH_TRY(sum_prepare(k, ops + t0, scale + t0, sign + t0, d, m, a, &strided, false, "jh_blocksum_mul", scale_flags ? scale_flags + t0 : nullptr, &wide));
         const int acc = t0 > 0 ? 1 : 0;
-        int st = JH_OK;
-        switch (ops[0]->dtype) {
-        case JH_F32: st = sum_fwd_launch<float, 1, 4>(a, strided, ops[0], d->data, m->data, n, acc, wide); break;
-        case JH_F64: st = sum_fwd_launch<double, 1, 2>(a, strided, ops[0], d->data, m->data, n, acc); break;
-        case JH_C32: st = sum_fwd_launch<float, 2, 4>(a, strided, ops[0], d->data, m->data, 2 * n, acc, wide); break;
-        case JH_C64: st = sum_fwd_launch<double, 2, 2>(a, strided, ops[0], d->data, m->data, 2 * n, acc); break;
-        default: return jh_fail(JH_ERR_INVALID, "jh_blocksum_mul: unknown dtype");
-        }
-        JH_TRY(st);
+        JH_TRY(jh_by_dtype(ops[0]->dtype, "jh_blocksum_mul", [&](auto t) {
+            using T = decltype(t);
+            if constexpr (sizeof(typename T::S) == 4) return sum_fwd_launch<typename T::S, T::E, T::NS>(a, strided, ops[0], d->data, m->data, n * T::E, acc, wide);
+            else return sum_fwd_launch<typename T::S, T::E, T::NS>(a, strided, ops[0], d->data, m->data, n * T::E, acc);
+        }));
     }
     return JH_OK;
 }
@@ -569,25 +568,21 @@ int jh_blocksum_mul_adj_typed(int nterms, const jh_blockop *const *ops, const do
     bool any_wide = false;
     if (scale_flags && (ops[0]->dtype == JH_F32 || ops[0]->dtype == JH_C32))
         for (int t = 0; t < nterms; t++) any_wide = any_wide || (scale_flags[t] & JH_SCALAR_WIDE);
-    switch (ops[0]->dtype) {
-#define JH_SUM_ADJ(S, E, NS, NSCAL)                                                                         \
-    if (!any_wide) JH_TRY(jhb::split_adjoint_tmp(ops[0], &tmp));   /* (a wide scale is applied per d_i before the sum: the ordered walk) */ \
-    if (tmp) return sum_adj_split<S, E, NS>(nterms, ops, scale, sign, m->data, d->data, NSCAL, tmp);      \
-    for (int t0 = 0; t0 < nterms; t0 += group) {                                                            \
-        const int k = nterms - t0 < group ? nterms - t0 : group;                                            \
-        SumArgs a;                                                                                          \
-        bool wide = false, strided = false;                                                                 \
-        JH_TRY(sum_prepare(k, ops + t0, scale + t0, sign + t0, d, m, a, &strided, true, "jh_blocksum_mul_adj", scale_flags ? scale_flags + t0 : nullptr, &wide)); \
-        JH_TRY((sum_adj_launch<S, E, NS>(a, strided, ops[0], m->data, d->data, NSCAL, t0 > 0 ? 1 : 0, wide)));  \
-    }                                                                                                       \
-    return JH_OK;
-    case JH_F32: JH_SUM_ADJ(float, 1, 4, n)
-    case JH_F64: JH_SUM_ADJ(double, 1, 2, n)
-    case JH_C32: JH_SUM_ADJ(float, 2, 4, 2 * n)
-    case JH_C64: JH_SUM_ADJ(double, 2, 2, 2 * n)
-#undef JH_SUM_ADJ
-    }
-    return jh_fail(JH_ERR_INVALID, "jh_blocksum_mul_adj: unknown dtype");
+    return jh_by_dtype(ops[0]->dtype, "jh_blocksum_mul_adj", [&](auto t) -> int {
+        using T = decltype(t);
+        using S = typename T::S;
+        constexpr int E = T::E, NS = T::NS;
+        if (!any_wide) JH_TRY(jhb::split_adjoint_tmp(ops[0], &tmp));   // (a wide scale is applied per d_i before the sum: the ordered walk)
+        if (tmp) return sum_adj_split<S, E, NS>(nterms, ops, scale, sign, m->data, d->data, n * E, tmp);
+        for (int t0 = 0; t0 < nterms; t0 += group) {
+            const int k = nterms - t0 < group ? nterms - t0 : group;
+            SumArgs a;
+            bool wide = false, strided = false;
+            JH_TRY(sum_prepare(k, ops + t0, scale + t0, sign + t0, d, m, a, &strided, true, "jh_blocksum_mul_adj", scale_flags ? scale_flags + t0 : nullptr, &wide));
+            JH_TRY((sum_adj_launch<S, E, NS>(a, strided, ops[0], m->data, d->data, n * E, t0 > 0 ? 1 : 0, wide)));
+        }
+        return JH_OK;
+    });
 }
 
 

@@ -624,13 +624,10 @@ int reduce_blocks_launch(const jh_bvec *x, const jh_bvec *y, double p, double *h
 template <int OP>
 int reduce_blocks_dispatch(const jh_bvec *x, const jh_bvec *y, double p, double *host_out)
 {
-    switch (x->dtype) {
-    case JH_F32: return reduce_blocks_launch<float, 1, OP>(x, y, p, host_out);
-    case JH_F64: return reduce_blocks_launch<double, 1, OP>(x, y, p, host_out);
-    case JH_C32: return reduce_blocks_launch<float, 2, OP>(x, y, p, host_out);
-    case JH_C64: return reduce_blocks_launch<double, 2, OP>(x, y, p, host_out);
-    }
-    return jh_fail(JH_ERR_INVALID, "unknown dtype %d", x->dtype);
+    return jh_by_dtype(x->dtype, "blockwise reduction", [&](auto t) {
+        using T = decltype(t);
+        return reduce_blocks_launch<typename T::S, T::E, OP>(x, y, p, host_out);
+    });
 }
 
 template <typename S, int E, int OP>
@@ -671,13 +668,10 @@ int reduce_launch(const void *x, const void *y, int64_t n_elems, double p, doubl
 template <int OP>
 int reduce_dispatch(int dtype, const void *x, const void *y, int64_t n, double p, double *r0, double *r1, double scale = 1.0)
 {
-    switch (dtype) {
-    case JH_F32: return reduce_launch<float, 1, OP>(x, y, n, p, r0, r1, scale);
-    case JH_F64: return reduce_launch<double, 1, OP>(x, y, n, p, r0, r1, scale);
-    case JH_C32: return reduce_launch<float, 2, OP>(x, y, n, p, r0, r1, scale);
-    case JH_C64: return reduce_launch<double, 2, OP>(x, y, n, p, r0, r1, scale);
-    }
-    return jh_fail(JH_ERR_INVALID, "unknown dtype %d", dtype);
+    return jh_by_dtype(dtype, "reduction", [&](auto t) {
+        using T = decltype(t);
+        return reduce_launch<typename T::S, T::E, OP>(x, y, n, p, r0, r1, scale);
+    });
 }
 
 template <typename S, int E, bool WIDE>
@@ -729,13 +723,10 @@ int hadamard_launch(void *dst, const void *x, const void *y, int64_t n_elems, in
 
 int jh_launch_hadamard_raw(void *dst, const void *x, const void *y, int dtype, int64_t count, int conj_x)
 {
-    switch (dtype) {
-    case JH_F32: return hadamard_launch<float, 1>(dst, x, y, count, conj_x);
-    case JH_F64: return hadamard_launch<double, 1>(dst, x, y, count, conj_x);
-    case JH_C32: return hadamard_launch<float, 2>(dst, x, y, count, conj_x);
-    case JH_C64: return hadamard_launch<double, 2>(dst, x, y, count, conj_x);
-    }
-    return jh_fail(JH_ERR_INVALID, "hadamard: unknown dtype %d", dtype);
+    return jh_by_dtype(dtype, "hadamard", [&](auto t) {
+        using T = decltype(t);
+        return hadamard_launch<typename T::S, T::E>(dst, x, y, count, conj_x);
+    });
 }
 
 int jh_launch_square_jvp_raw(void *dst, const void *mo, const void *x, int dtype, int64_t count, int conj_mo)
@@ -750,13 +741,11 @@ int jh_launch_lincomb_raw(void *dst, int dtype, int64_t count, int k, const doub
     a.k = k;
     for (int j = 0; j < k; j++) { a.x[j] = x[j]; a.cre[j] = cre[j]; a.cim[j] = cim[j]; }
     const bool wide = lincomb_args_flags(a, flags, dtype);
-    switch (dtype) {
-    case JH_F32: return lincomb_launch<float, 1>(dst, count, a, wide);
-    case JH_F64: return lincomb_launch<double, 1>(dst, count, a);
-    case JH_C32: return lincomb_launch<float, 2>(dst, count, a, wide);
-    case JH_C64: return lincomb_launch<double, 2>(dst, count, a);
-    }
-    return jh_fail(JH_ERR_INVALID, "lincomb: unknown dtype %d", dtype);
+    return jh_by_dtype(dtype, "lincomb", [&](auto t) {
+        using T = decltype(t);
+        if constexpr (sizeof(typename T::S) == 4) return lincomb_launch<typename T::S, T::E>(dst, count, a, wide);
+        else return lincomb_launch<typename T::S, T::E>(dst, count, a);
+    });
 }
 
 // device-to-device copy of `bytes` bytes: own streaming kernel when both ends are 16-byte aligned and large,
@@ -779,13 +768,11 @@ int jh_launch_copy_bytes(void *dst, const void *src, size_t bytes)
 
 int jh_launch_fill_range(void *ptr, int dtype, int64_t count, double re, double im)
 {
-    switch (dtype) {
-    case JH_F32: return fill_scalars<float, 1>((float *)ptr, count, re, 0);
-    case JH_F64: return fill_scalars<double, 1>((double *)ptr, count, re, 0);
-    case JH_C32: return fill_scalars<float, 2>((float *)ptr, 2 * count, re, im);
-    case JH_C64: return fill_scalars<double, 2>((double *)ptr, 2 * count, re, im);
-    }
-    return jh_fail(JH_ERR_INVALID, "fill: unknown dtype %d", dtype);
+    return jh_by_dtype(dtype, "fill", [&](auto t) {
+        using T = decltype(t);
+        using S = typename T::S;
+        return fill_scalars<S, T::E>((S *)ptr, count * T::E, re, T::E == 2 ? im : 0);
+    });
 }
 
 extern "C" {
@@ -841,14 +828,13 @@ int jh_abs(jh_bvec *dst, const jh_bvec *x)
     if (x->length == 0) return JH_OK;
     hipStream_t st = jh_ctx().stream;
     const int g = grid_full(x->length);
-    switch (x->dtype) {
-    case JH_F32: hipLaunchKernelGGL((k_abs<float, 1>), dim3(g), dim3(WG), 0, st, (float *)dst->data, (const float *)x->data, x->length); break;
-    case JH_F64: hipLaunchKernelGGL((k_abs<double, 1>), dim3(g), dim3(WG), 0, st, (double *)dst->data, (const double *)x->data, x->length); break;
-    case JH_C32: hipLaunchKernelGGL((k_abs<float, 2>), dim3(g), dim3(WG), 0, st, (float *)dst->data, (const float *)x->data, x->length); break;
-    case JH_C64: hipLaunchKernelGGL((k_abs<double, 2>), dim3(g), dim3(WG), 0, st, (double *)dst->data, (const double *)x->data, x->length); break;
-    }
-    JH_CHECK_HIP(hipGetLastError());
-    return JH_OK;
+    return jh_by_dtype(x->dtype, "jh_abs", [&](auto t) -> int {
+        using T = decltype(t);
+        using S = typename T::S;
+        hipLaunchKernelGGL((k_abs<S, T::E>), dim3(g), dim3(WG), 0, st, (S *)dst->data, (const S *)x->data, x->length);
+        JH_CHECK_HIP(hipGetLastError());
+        return JH_OK;
+    });
 }
 
 int jh_lincomb_typed(jh_bvec *dst, int k, const double *coef, const int32_t *coef_flags, const jh_bvec *const *x)
@@ -873,13 +859,11 @@ int jh_lincomb_typed(jh_bvec *dst, int k, const double *coef, const int32_t *coe
         a.cim[j] = coef[2 * j + 1];
     }
     const bool wide = lincomb_args_flags(a, coef_flags, dst->dtype);
-    switch (dst->dtype) {
-    case JH_F32: return lincomb_launch<float, 1>(dst->data, dst->length, a, wide);
-    case JH_F64: return lincomb_launch<double, 1>(dst->data, dst->length, a);
-    case JH_C32: return lincomb_launch<float, 2>(dst->data, dst->length, a, wide);
-    case JH_C64: return lincomb_launch<double, 2>(dst->data, dst->length, a);
-    }
-    return jh_fail(JH_ERR_INVALID, "jh_lincomb: unknown dtype %d", dst->dtype);
+    return jh_by_dtype(dst->dtype, "jh_lincomb", [&](auto t) {
+        using T = decltype(t);
+        if constexpr (sizeof(typename T::S) == 4) return lincomb_launch<typename T::S, T::E>(dst->data, dst->length, a, wide);
+        else return lincomb_launch<typename T::S, T::E>(dst->data, dst->length, a);
+    });
 }
 
 int jh_lincomb(jh_bvec *dst, int k, const double *coef, const jh_bvec *const *x) { return jh_lincomb_typed(dst, k, coef, nullptr, x); }
@@ -892,13 +876,10 @@ int jh_hadamard(jh_bvec *dst, const jh_bvec *x, const jh_bvec *y, int conj_x)
     JH_REQUIRE(conj_x >= 0 && conj_x <= 3, "jh_hadamard: flags must be 0..3 (got %d)", conj_x);
     JH_REQUIRE(dst->length == x->length && dst->length == y->length, "jh_hadamard: length mismatch (%lld, %lld, %lld)",
                (long long)dst->length, (long long)x->length, (long long)y->length);
-    switch (dst->dtype) {
-    case JH_F32: return hadamard_launch<float, 1>(dst->data, x->data, y->data, dst->length, conj_x);
-    case JH_F64: return hadamard_launch<double, 1>(dst->data, x->data, y->data, dst->length, conj_x);
-    case JH_C32: return hadamard_launch<float, 2>(dst->data, x->data, y->data, dst->length, conj_x);
-    case JH_C64: return hadamard_launch<double, 2>(dst->data, x->data, y->data, dst->length, conj_x);
-    }
-    return jh_fail(JH_ERR_INVALID, "jh_hadamard: unknown dtype %d", dst->dtype);
+    return jh_by_dtype(dst->dtype, "jh_hadamard", [&](auto t) {
+        using T = decltype(t);
+        return hadamard_launch<typename T::S, T::E>(dst->data, x->data, y->data, dst->length, conj_x);
+    });
 }
 
 int jh_dot(const jh_bvec *x, const jh_bvec *y, double *re, double *im)
