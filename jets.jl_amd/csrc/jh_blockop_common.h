@@ -163,6 +163,13 @@ template <typename S, int E> inline DiagBase<S> diag_base(const jh_blockop *op)
 {
     return {op->diag_strided ? (const S *)op->blocks[0].coeff : nullptr, op->diag_stride_elems * E};
 }
+// vectors aligned like their scalar (the under-aligned packs above take any such address; c may be NULL)
+inline bool vectors_scalar_aligned(int dtype, const void *a, const void *b, const void *c = nullptr)
+{
+    const size_t es = jh_dtype_size(dtype), sa = jh_dtype_complex(dtype) ? es / 2 : es;
+    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & (sa - 1)) == 0;
+}
+struct RowParts { int64_t parts, rows_per_part; };   // a split-row walk: workgroup row y sums rows [y, y + 1) * rows_per_part; one part: the ordered walk over all nrow
 
 namespace jhb {
 // ---- jh_tall.hip
@@ -171,6 +178,7 @@ bool tall_mixed_ok(const jh_blockop *op, const void *rng_ptr, const void *dom_pt
 bool tall_unaligned_ok(const jh_blockop *op, const void *rng_ptr, const void *dom_ptr);   // the same without the 16-byte conditions (whole-vector forward / adjoint / A'A)
 TallShape pick_adj_shape(int64_t nvec, int64_t nrow, int mode);
 int64_t pick_adj_parts(int64_t gx, int64_t nrow);
+RowParts pick_row_parts(int64_t span, int NS, int64_t gx, int64_t nrow);   // the part rule of the grid kernels and the tall chains: `span` scalars in gx workgroups of packs of NS
 // ---- jh_tall_chain.hip
 int bare_chain(const jh_blockop *op, void *out, const void *in, int mode, bool *took);   // the ADJOINT (mode 0) / NORMAL (1) chain kernel with empty stage lists as jh_blockop_mul_adj / _normal_mul of mixed / off-grid rows up to 4 MiB
 // ---- jh_grid_normal.hip

@@ -9,26 +9,12 @@ int grid_chain_launch_normal(const jh_chain *ch, int prog, void *out, const void
 
 // may jh_chain_create build a grid chain on `op`?  An N x K grid, N >= 2, K = 2 .. 4, of equal blocks of >= 16 bytes, every block a diagonal, an
 // adjointed diagonal, a zero, an identity or a scalar (the kinds of k_grid_normal_mixed), no nonlinear child, coefficients aligned like their scalar;
-// knob grid_chain = 1
-bool grid_chain_ok(const jh_blockop *op)
-{
-    if (jh_ctx().grid_chain == 0) return false;
-    if (op->tall || op->nrow < 2 || op->ncol < 2 || op->ncol > 4 || !op->uniform_rows || !op->elementwise || op->nonlinear || op->wide_scale) return false;
-    for (const jh_block_desc &b : op->blocks)
-        if (b.kind != JH_OP_ZERO && b.kind != JH_OP_IDENTITY && b.kind != JH_OP_SCALE && b.kind != JH_OP_DIAG) return false;
-    const int64_t n = op->row_len[0];
-    if (n * (int64_t)jh_dtype_size(op->dtype) < 16) return false;
-    for (int64_t v : op->col_len)
-        if (v != n) return false;
-    return op->coeff_scalar_aligned;
-}
+// knob grid_chain = 1.  That is grid_shape_ok(op, true): an operator is tall only with one block column, and jh_blockop_create leaves all_diag set only
+// where every block is a DIAG -- elementwise, linear, no wide scalar --, which is all that grid_shape_ok skips for plain diagonals
+bool grid_chain_ok(const jh_blockop *op) { return jh_ctx().grid_chain != 0 && grid_shape_ok(op, true); }
 
 // vectors aligned like their scalar (the under-aligned packs of jh_blockop_common.h take any such address)
-bool grid_chain_vectors_ok(const jh_blockop *op, const void *a, const void *b)
-{
-    const size_t es = jh_dtype_size(op->dtype), sa = jh_dtype_complex(op->dtype) ? es / 2 : es;
-    return ((((uintptr_t)a) | ((uintptr_t)b)) & (sa - 1)) == 0 && op->coeff_scalar_aligned;
-}
+bool grid_chain_vectors_ok(const jh_blockop *op, const void *a, const void *b) { return vectors_scalar_aligned(op->dtype, a, b) && op->coeff_scalar_aligned; }
 
 // out = chain(in) for chain type `type` over program `prog` (GRID_PROG_OWN: the handle's own; GRID_PROG_ADJ / _NRM: derived from a FORWARD chain)
 int grid_chain_launch(const jh_chain *ch, int prog, int type, void *out, const void *in, int accumulate)

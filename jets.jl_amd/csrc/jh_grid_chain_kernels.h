@@ -17,6 +17,7 @@
 // mid_prog reads a row's weight words at e[1 .. NW]: it is handed the record from word K - 1 on.
 #pragma once
 #include "jh_tall_chain_kernels.h"
+#include "jh_grid_common.h"
 
 namespace jhb {
 // k_chain_finish on `ch`'s element type (jh_tall_chain_adj.hip: the tall chains' instantiations, not a second copy per grid unit)
@@ -169,93 +170,70 @@ __global__ __launch_bounds__(256) void k_grid_chain(const jh_dev_block *__restri
 // rows in flight: two for every K (K x 2 coefficient packs per lane, and the weights'); K = 2 at four rows spilled SGPRs with two range weights
 template <int K> struct grid_chain_depth { static constexpr int value = 2; };
 
+// first match of (nontemporal, range-side coefficient streams)
+template <typename S, int E, int NS, int K, int MODE> struct GridChainPicker {
+    static constexpr int D = grid_chain_depth<K>::value;
+    using Kernel = decltype(&k_grid_chain<S, E, NS, K, D, false, MODE, 0>);
+    bool nt;
+    int nw;
+    Picked<Kernel> got;
+    template <bool NTV, int NWV> bool row()
+    {
+        if (nt == NTV && nw == NWV) got = {&k_grid_chain<S, E, NS, K, D, NTV, MODE, NWV>, 256, 1, D};
+        return got.k != nullptr;
+    }
+    Picked<Kernel> pick() { (void)(row<false, 0>() || row<true, 0>() || row<false, 1>() || row<true, 1>() || row<false, 2>() || row<true, 2>()); return got; }
+};
+
 // end_elem < 0: the whole block; else the positions [first_elem, end_elem) of every block (jh_chain_apply_range, MODE != 0; the caller has checked the
-// bounds): the same kernel over those lanes.  The parts are chosen from the RANGE's pack count, the slabs keep the block's stride (parts x K x n_scalars,
-// of which a range touches its share), the fold and the list after A' run over each of the K pieces' range, and the nontemporal rule sees the WHOLE
-// vector's bytes, so that a range streams like the whole vector.
+// bounds): the same kernel over those lanes (GridPlan, jh_grid_common.h), the list after A' over each of the K pieces' range like the fold, and the
+// nontemporal rule sees the WHOLE vector's bytes, so that a range streams like the whole vector.
 template <typename S, int E, int NS, int K, int MODE>
-int launch_grid_chain_k(const jh_chain *ch, int prog, void *out, const void *in, int64_t n_scalars, int accumulate, int64_t first_elem, int64_t end_elem)
+int launch_grid_chain_k(const jh_chain *ch, int prog, void *out, const void *in, int accumulate, int64_t first_elem, int64_t end_elem)
 {
     const ChainArgs &ca = prog == GRID_PROG_ADJ ? ch->adj_args : (prog == GRID_PROG_NRM ? ch->nrm_args : ch->args);
-    constexpr int DEPTH = grid_chain_depth<K>::value;
     jh_context &c = jh_ctx();
     const jh_blockop *op = ch->op;
-    const bool ranged = end_elem >= 0;
-    const int64_t s_begin = ranged ? first_elem * E : 0, s_end = ranged ? end_elem * E : n_scalars;
-    const int64_t packs = (s_end - s_begin + NS - 1) / NS, gx = (packs + 255) / 256, ndom = (int64_t)K * n_scalars;
-    int64_t parts = 1, rows_per_part = op->nrow;
+    GridPlan p = MODE == 0 ? grid_lanes(op, E, NS, first_elem, end_elem) : grid_plan(op, E, NS, first_elem, end_elem);
     if (MODE == 0) {
         // FORWARD: the rows are independent; row groups of their own workgroups where one walk per tile would leave the chip short of
         // workgroups (P(m) is formed once per group: K n s more bytes per extra group).  adj_split > 1 forces the count.
-        const int64_t want = (4 * (int64_t)c.cu_count + gx - 1) / gx;
-        parts = c.adj_split > 1 ? c.adj_split : (c.adj_split == 0 ? 1 : want);
-    } else {
-        // the part-count rules of the tall chains and k_grid_normal (jh_tall.hip: pick_adj_parts; adj_split = 0 keeps the ordered, bit-exact walk)
-        parts = jhb::pick_adj_parts(gx, op->nrow);
-        if (parts == 1 && c.adj_split < 0 && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
-        if (s_end - s_begin < NS) parts = 1;                                             // (a range shorter than one pack loads from before s_begin: one part)
+        const int64_t want = (4 * (int64_t)c.cu_count + p.gx - 1) / p.gx;
+        p.parts = c.adj_split > 1 ? c.adj_split : (c.adj_split == 0 ? 1 : want);
+        if (p.parts > op->nrow) p.parts = op->nrow;
+        if (p.parts < 1) p.parts = 1;
+        p.rows_per_part = (op->nrow + p.parts - 1) / p.parts;
+        p.parts = (op->nrow + p.rows_per_part - 1) / p.rows_per_part;
+        JH_REQUIRE(p.parts < 65536, "grid chain: %lld row parts", (long long)p.parts);
     }
-    if (parts > op->nrow) parts = op->nrow;
-    if (parts < 1) parts = 1;
-    if (parts > 1) {
-        rows_per_part = (op->nrow + parts - 1) / parts;
-        parts = (op->nrow + rows_per_part - 1) / rows_per_part;
-    }
-    JH_REQUIRE(parts < 65536, "grid chain: %lld row parts", (long long)parts);
     const bool finish = MODE != 0 && (accumulate != 0 || (ca.post.st[0] & 15u) != CK_NONE);
-    S *slabs = nullptr, *folded = (S *)out;
-    if (MODE != 0 && parts > 1) {
-        void *sp = nullptr;
-        JH_TRY(jhb::split_slabs(out, (size_t)(parts + (finish ? 1 : 0)) * (size_t)ndom * sizeof(S), &sp));
-        slabs = (S *)sp;
-        if (finish) folded = slabs + parts * ndom;
+    S *slabs = nullptr;
+    if (MODE != 0) {
+        JH_TRY(grid_slabs(p, K, out, &slabs, finish));
+        c.last_adj_parts = p.parts;
     }
-    if (MODE != 0) c.last_adj_parts = parts;
     const ChainProg *mid_dev = ch->dev_mid + prog;                                      // (ca.mid's device copy: the kernel reads it per row)
-    const double streamed = ch->stream_bytes + (MODE != 2 ? (double)op->nrow * (double)n_scalars * sizeof(S) : 0.0);
+    const double streamed = ch->stream_bytes + (MODE != 2 ? (double)op->nrow * (double)p.n_scalars * sizeof(S) : 0.0);
     const bool nt = jh_stream_nt(streamed);
-    if (ranged) c.last_grid_chain_range_shape = (nt ? 1 : 0) | (parts > 1 ? 2 : 0);
-    else c.last_grid_chain_shape = (nt ? 1 : 0) | (parts > 1 ? 2 : 0) | (finish && parts > 1 ? 4 : 0);
-#define JH_GRID_CHAIN(NTV, NWV)                                                                                                              \
-    hipLaunchKernelGGL((k_grid_chain<S, E, NS, K, DEPTH, NTV, MODE, NWV>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, op->dev_blocks, \
-                       op->nrow, ca, (S *)out, (const S *)in, n_scalars, accumulate, rows_per_part, slabs, mid_dev, s_begin, s_end)
-    switch (ch->nw) {
-    case 0: if (nt) JH_GRID_CHAIN(true, 0); else JH_GRID_CHAIN(false, 0); break;
-    case 1: if (nt) JH_GRID_CHAIN(true, 1); else JH_GRID_CHAIN(false, 1); break;
-    default: if (nt) JH_GRID_CHAIN(true, 2); else JH_GRID_CHAIN(false, 2); break;
-    }
-#undef JH_GRID_CHAIN
+    if (p.ranged) c.last_grid_chain_range_shape = (nt ? 1 : 0) | (p.parts > 1 ? 2 : 0);
+    else c.last_grid_chain_shape = (nt ? 1 : 0) | (p.parts > 1 ? 2 : 0) | (finish && p.parts > 1 ? 4 : 0);
+    const auto k = GridChainPicker<S, E, NS, K, MODE>{nt, ch->nw < 2 ? ch->nw : 2, {}}.pick();
+    JH_REQUIRE(k.k, "grid chain: no kernel for %d range-side streams", ch->nw);
+    hipLaunchKernelGGL(k.k, dim3((unsigned)p.gx, (unsigned)p.parts), dim3(k.blk), 0, c.stream, op->dev_blocks, op->nrow, ca, (S *)out, (const S *)in,
+                       p.n_scalars, accumulate, p.rows_per_part, slabs, mid_dev, p.s_begin, p.s_end);
     JH_CHECK_HIP(hipGetLastError());
-    if (slabs && !ranged) {
-        JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, ndom, parts, folded, 0, ndom));
-        if (finish) {
-            JH_TRY(jhb::chain_finish(ch, ca, out, folded, 0, ndom, accumulate));
-        }
-    }
-    if (slabs && ranged)                                                                 // (the slabs keep the whole block's stride: the range of each piece)
-        for (int k = 0; k < K; k++) {
-            const int64_t lo = (int64_t)k * n_scalars + s_begin, hi = (int64_t)k * n_scalars + s_end;
-            JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs + lo, ndom, parts, folded, lo, hi));
-            if (finish) JH_TRY(jhb::chain_finish(ch, ca, out, folded, lo, hi, accumulate));
-        }
-    return JH_OK;
+    return grid_fold(p, K, slabs, out, finish, [&](const void *folded, int64_t lo, int64_t hi) { return jhb::chain_finish(ch, ca, out, folded, lo, hi, accumulate); });
 }
 
 // first_elem, end_elem: positions inside a block (end_elem < 0: the whole block)
 template <int MODE>
 int launch_grid_chain(const jh_chain *ch, int prog, void *out, const void *in, int accumulate, int64_t first_elem = 0, int64_t end_elem = -1)
 {
-    const jh_blockop *op = ch->op;
-    const int64_t n = op->row_len[0];
-    return jh_by_dtype(op->dtype, "grid chain", [&](auto t) {
+    return jh_by_dtype(ch->op->dtype, "grid chain", [&](auto t) {
         using T = decltype(t);
-        using S = typename T::S;
-        constexpr int E = T::E, NS = T::NS;
-        switch (op->ncol) {
-        case 2: return launch_grid_chain_k<S, E, NS, 2, MODE>(ch, prog, out, in, n * E, accumulate, first_elem, end_elem);
-        case 3: return launch_grid_chain_k<S, E, NS, 3, MODE>(ch, prog, out, in, n * E, accumulate, first_elem, end_elem);
-        default: return launch_grid_chain_k<S, E, NS, 4, MODE>(ch, prog, out, in, n * E, accumulate, first_elem, end_elem);
-        }
+        return grid_by_k(ch->op->ncol, [&](auto k) {
+            return launch_grid_chain_k<typename T::S, T::E, T::NS, decltype(k)::value, MODE>(ch, prog, out, in, accumulate, first_elem, end_elem);
+        });
     });
 }
 

@@ -12,7 +12,7 @@
 // and k_grid_step), keeps P(v)_1 .. P(v)_K and w_1 .. w_K in registers and walks the block rows in order, DEPTH rows of loads in flight: every
 // coefficient and every weight is read once, u_i is read (beta != 0), updated and written between R and R^H.  (N K + (NW + 2) N + 2 K) n s bytes; u
 // and w keep the bits of the three-call route (-ffp-contract=off), ||u||^2 counts each scalar once from the lane that owns it (vnorm2_from).
-// Many rows of small blocks take the split-row walk (the part rules of launch_grid_chain_k, MODE != 0): u is updated row by row either way (same
+// Many rows of small blocks take the split-row walk (grid_plan, jh_grid_common.h): u is updated row by row either way (same
 // bits); w is summed per part, folded, and Q follows on the folded vector (k_chain_finish) -- tolerance parity; adj_split = 0: the ordered walk.
 #include "jh_grid_chain_kernels.h"
 
@@ -153,74 +153,48 @@ template <typename S, int K, int NW, bool OLD> struct grid_chain_step_depth {
     static constexpr int value = (sizeof(S) == 4 && NW == 2 && K + (OLD ? 1 : 0) >= 4) ? 1 : 2;
 };
 
+// first match of (nontemporal, range-side coefficient streams, u read: beta != 0)
+template <typename S, int E, int NS, int K> struct GridChainStepPicker {
+    using Kernel = decltype(&k_grid_chain_step<S, E, NS, K, 1, false, 0, false>);
+    bool nt;
+    int nw;
+    bool old;
+    Picked<Kernel> got;
+    template <bool NTV, int NWV, bool OLDV> bool row()
+    {
+        constexpr int D = grid_chain_step_depth<S, K, NWV, OLDV>::value;
+        if (nt == NTV && nw == NWV && old == OLDV) got = {&k_grid_chain_step<S, E, NS, K, D, NTV, NWV, OLDV>, 256, 1, D};
+        return got.k != nullptr;
+    }
+    template <int NWV> bool rows() { return row<false, NWV, false>() || row<true, NWV, false>() || row<false, NWV, true>() || row<true, NWV, true>(); }
+    Picked<Kernel> pick() { (void)(rows<0>() || rows<1>() || rows<2>()); return got; }
+};
+
 // end_elem < 0: the whole block; else the positions [first_elem, end_elem) of every block (jh_chain_bidiag_step_range, knob grid_chain_range): the same
-// kernel over those lanes, the parts chosen from the RANGE's pack count, the slabs at the block's stride, the fold and Q over each of the K pieces'
-// range, ||u||^2 deferred (normsq == NULL: added to the context's accumulator in enqueue order)
+// kernel over those lanes (GridPlan), Q over each of the K pieces' range, ||u||^2 deferred (normsq == NULL: added to the context's accumulator in enqueue order)
 template <typename S, int E, int NS, int K>
-int launch_grid_chain_step_k(const jh_chain *ch, void *u, const void *v, void *w, int64_t n_scalars, double alpha, double beta, double *normsq,
-                             int64_t first_elem, int64_t end_elem)
+int launch_grid_chain_step_k(const jh_chain *ch, void *u, const void *v, void *w, double alpha, double beta, double *normsq, int64_t first_elem, int64_t end_elem)
 {
     const ChainArgs &ca = ch->step_args;
     jh_context &c = jh_ctx();
     const jh_blockop *op = ch->op;
-    const bool ranged = end_elem >= 0;
-    const int64_t s_begin = ranged ? first_elem * E : 0, s_end = ranged ? end_elem * E : n_scalars;
-    const int64_t packs = (s_end - s_begin + NS - 1) / NS, gx = (packs + 255) / 256, ndom = (int64_t)K * n_scalars;
-    // the part-count rules of the grid chains' ADJOINT / NORMAL walks (launch_grid_chain_k; adj_split = 0 keeps the ordered, bit-exact walk)
-    int64_t parts = jhb::pick_adj_parts(gx, op->nrow), rows_per_part = op->nrow;
-    if (parts == 1 && c.adj_split < 0 && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
-    if (s_end - s_begin < NS) parts = 1;                                                 // (a range shorter than one pack loads from before s_begin: one part)
-    if (parts > op->nrow) parts = op->nrow;
-    if (parts < 1) parts = 1;
-    if (parts > 1) {
-        rows_per_part = (op->nrow + parts - 1) / parts;
-        parts = (op->nrow + rows_per_part - 1) / rows_per_part;
-    }
-    JH_REQUIRE(parts < 65536, "grid chain step: %lld row parts", (long long)parts);
+    const GridPlan p = grid_plan(op, E, NS, first_elem, end_elem);
     const bool finish = (ca.post.st[0] & 15u) != CK_NONE;
-    S *slabs = nullptr, *folded = (S *)w;
-    if (parts > 1) {
-        void *sp = nullptr;
-        JH_TRY(jhb::split_slabs(w, (size_t)(parts + (finish ? 1 : 0)) * (size_t)ndom * sizeof(S), &sp));
-        slabs = (S *)sp;
-        if (finish) folded = slabs + parts * ndom;
-    }
-    JH_TRY(jh_ensure_partials(gx * parts));
+    S *slabs = nullptr;
+    JH_TRY(grid_slabs(p, K, w, &slabs, finish));
+    JH_TRY(jh_ensure_partials(p.gx * p.parts));
     // streamed per pass: the coefficients and the weights, and u -- written, and read as well when beta != 0
-    const bool nt = jh_stream_nt(ch->stream_bytes + (beta != 0.0 ? 2.0 : 1.0) * (double)op->nrow * (double)n_scalars * sizeof(S));
-    c.last_adj_parts = parts;
-    (ranged ? c.last_grid_chain_range_shape : c.last_grid_chain_step_shape) = (nt ? 1 : 0) | (parts > 1 ? 2 : 0);
+    const bool nt = jh_stream_nt(ch->stream_bytes + (beta != 0.0 ? 2.0 : 1.0) * (double)op->nrow * (double)p.n_scalars * sizeof(S));
+    c.last_adj_parts = p.parts;
+    (p.ranged ? c.last_grid_chain_range_shape : c.last_grid_chain_step_shape) = (nt ? 1 : 0) | (p.parts > 1 ? 2 : 0);
     const ChainProg *mid_dev = ch->dev_mid + GRID_PROG_OWN;                              // (R: the FORWARD chain's own range-side list)
-#define JH_GCS(NTV, NWV, OLDV)                                                                                                               \
-    hipLaunchKernelGGL((k_grid_chain_step<S, E, NS, K, grid_chain_step_depth<S, K, NWV, OLDV>::value, NTV, NWV, OLDV>), dim3((unsigned)gx, (unsigned)parts), \
-                       dim3(256), 0, c.stream, op->dev_blocks, op->nrow, ca, (S *)w, (const S *)v, (S *)u, n_scalars, (S)alpha, (S)beta, c.part_dev,   \
-                       rows_per_part, slabs, mid_dev, s_begin, s_end)
-#define JH_GCS_OLD(NTV, NWV)                   \
-    if (beta != 0.0) JH_GCS(NTV, NWV, true);   \
-    else JH_GCS(NTV, NWV, false)
-#define JH_GCS_NT(NWV)                 \
-    if (nt) { JH_GCS_OLD(true, NWV); } \
-    else { JH_GCS_OLD(false, NWV); }
-    switch (ch->nw) {
-    case 0: JH_GCS_NT(0) break;
-    case 1: JH_GCS_NT(1) break;
-    default: JH_GCS_NT(2) break;
-    }
-#undef JH_GCS_NT
-#undef JH_GCS_OLD
-#undef JH_GCS
+    const auto k = GridChainStepPicker<S, E, NS, K>{nt, ch->nw < 2 ? ch->nw : 2, beta != 0.0, {}}.pick();
+    JH_REQUIRE(k.k, "grid chain step: no kernel for %d range-side streams", ch->nw);
+    hipLaunchKernelGGL(k.k, dim3((unsigned)p.gx, (unsigned)p.parts), dim3(k.blk), 0, c.stream, op->dev_blocks, op->nrow, ca, (S *)w, (const S *)v, (S *)u,
+                       p.n_scalars, (S)alpha, (S)beta, c.part_dev, p.rows_per_part, slabs, mid_dev, p.s_begin, p.s_end);
     JH_CHECK_HIP(hipGetLastError());
-    if (slabs && !ranged) {
-        JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, ndom, parts, folded, 0, ndom));
-        if (finish) JH_TRY(jhb::chain_finish(ch, ca, w, folded, 0, ndom, 0));
-    }
-    if (slabs && ranged)                                                                 // (the slabs keep the whole block's stride: the range of each piece)
-        for (int k = 0; k < K; k++) {
-            const int64_t lo = (int64_t)k * n_scalars + s_begin, hi = (int64_t)k * n_scalars + s_end;
-            JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs + lo, ndom, parts, folded, lo, hi));
-            if (finish) JH_TRY(jhb::chain_finish(ch, ca, w, folded, lo, hi, 0));
-        }
-    return jhb::step_finish_normsq(gx * parts, normsq, ranged);
+    JH_TRY(grid_fold(p, K, slabs, w, finish, [&](const void *folded, int64_t lo, int64_t hi) { return jhb::chain_finish(ch, ca, w, folded, lo, hi, 0); }));
+    return jhb::step_finish_normsq(p.gx * p.parts, normsq, p.ranged);
 }
 
 }  // namespace
@@ -232,17 +206,11 @@ namespace jhb {
 static int grid_chain_step_by_dtype(const jh_chain *ch, void *u, const void *v, void *w, double alpha, double beta, double *normsq, int64_t first_elem,
                                     int64_t end_elem)
 {
-    const jh_blockop *op = ch->op;
-    const int64_t n = op->row_len[0];
-    return jh_by_dtype(op->dtype, "grid chain step", [&](auto t) {
+    return jh_by_dtype(ch->op->dtype, "grid chain step", [&](auto t) {
         using T = decltype(t);
-        using S = typename T::S;
-        constexpr int E = T::E, NS = T::NS;
-        switch (op->ncol) {
-        case 2: return launch_grid_chain_step_k<S, E, NS, 2>(ch, u, v, w, n * E, alpha, beta, normsq, first_elem, end_elem);
-        case 3: return launch_grid_chain_step_k<S, E, NS, 3>(ch, u, v, w, n * E, alpha, beta, normsq, first_elem, end_elem);
-        default: return launch_grid_chain_step_k<S, E, NS, 4>(ch, u, v, w, n * E, alpha, beta, normsq, first_elem, end_elem);
-        }
+        return grid_by_k(ch->op->ncol, [&](auto k) {
+            return launch_grid_chain_step_k<typename T::S, T::E, T::NS, decltype(k)::value>(ch, u, v, w, alpha, beta, normsq, first_elem, end_elem);
+        });
     });
 }
 

@@ -179,60 +179,43 @@ __global__ __launch_bounds__(256) void k_grid_normal(const jh_dev_block *__restr
     for (int k = 0; k < K; k++) st_pack<false, S, NS>(o + (int64_t)k * n_scalars, s0, sk, acc[k]);
 }
 
-template <typename S, int E, int NS, int K, int DEPTH>
+// rows in flight: K x DEPTH = 8 (6 for K = 3) coefficient packs per lane; 12 / 9 / 12 measured 2-3 % slower for K = 2 / 4 and within the noise for
+// K = 3 (profiles/bench_grid_normal_r06.txt)
+template <int K> struct grid_normal_depth { static constexpr int value = K == 2 ? 4 : 2; };
+
+// plain diagonals through the block table, or (MIXED) any grid through the packed one
+template <typename S, int E, int NS, int K, bool MIXED> auto pick_grid_normal(bool nt)
+{
+    constexpr int D = grid_normal_depth<K>::value;
+    if constexpr (MIXED) {
+        using P = Picked<decltype(&k_grid_normal_mixed<S, E, NS, K, D, false>)>;
+        return nt ? P{&k_grid_normal_mixed<S, E, NS, K, D, true>, 256, 1, D} : P{&k_grid_normal_mixed<S, E, NS, K, D, false>, 256, 1, D};
+    } else {
+        using P = Picked<decltype(&k_grid_normal<S, E, NS, K, D, false>)>;
+        return nt ? P{&k_grid_normal<S, E, NS, K, D, true>, 256, 1, D} : P{&k_grid_normal<S, E, NS, K, D, false>, 256, 1, D};
+    }
+}
+
+template <typename S, int E, int NS, int K>
 int launch_grid_normal(const jh_blockop *op, void *y, const void *m, int64_t first_elem, int64_t end_elem)
 {
     jh_context &c = jh_ctx();
-    // end_elem < 0: the whole block; else the positions [first_elem, end_elem) of every block, launched as a vector of its own length
-    const bool ranged = end_elem >= 0;
-    const int64_t n_scalars = op->row_len[0] * E, s_begin = ranged ? first_elem * E : 0, s_end = ranged ? end_elem * E : n_scalars;
-    const int64_t packs = (s_end - s_begin + NS - 1) / NS;
-    const int64_t gx = (packs + 255) / 256;
-    int64_t parts = s_end - s_begin < NS ? 1 : jhb::pick_adj_parts(gx, op->nrow), rows_per_part = 0;   // (a range shorter than one pack loads from before s_begin: one part)
-    // (one workgroup per CU, up to two: the ordered walk is latency-bound there, as for the chains -- jh_tall_chain.hip)
-    if (parts == 1 && s_end - s_begin >= NS && c.adj_split < 0 && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
-    void *slabs = nullptr;
-    if (parts > 1) {
-        rows_per_part = (op->nrow + parts - 1) / parts;
-        parts = (op->nrow + rows_per_part - 1) / rows_per_part;
-        JH_TRY(jhb::split_slabs(y, (size_t)parts * (size_t)K * (size_t)n_scalars * sizeof(S), &slabs));
-    }
-    c.last_adj_parts = parts;
+    const GridPlan p = grid_plan(op, E, NS, first_elem, end_elem);
+    S *slabs = nullptr;
+    JH_TRY(grid_slabs(p, K, y, &slabs));
+    c.last_adj_parts = p.parts;
     c.last_adj_launches = 1;
-    const bool nt = jh_stream_nt((double)op->nrow * (double)K * (double)n_scalars * sizeof(S));   // (a range too: the whole pass's bytes)
-    if (ranged) c.last_grid_range_shape = (nt ? 1 : 0) | (parts > 1 ? 2 : 0);
-    if (!op->all_diag) {                                       // (the packed table for grids of plain diagonals too: within the noise of this kernel, profiles/bench_grid_normal_r06.txt)
-        if (nt)
-            hipLaunchKernelGGL((k_grid_normal_mixed<S, E, NS, K, DEPTH, true>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, op->dev_blocks,
-                               (const uint64_t *)op->grid_words, op->nrow, n_scalars, (const S *)m, (S *)y, rows_per_part, (S *)slabs, s_begin, s_end);
-        else
-            hipLaunchKernelGGL((k_grid_normal_mixed<S, E, NS, K, DEPTH, false>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, op->dev_blocks,
-                               (const uint64_t *)op->grid_words, op->nrow, n_scalars, (const S *)m, (S *)y, rows_per_part, (S *)slabs, s_begin, s_end);
-    } else if (nt)
-        hipLaunchKernelGGL((k_grid_normal<S, E, NS, K, DEPTH, true>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, op->dev_blocks, op->nrow,
-                           n_scalars, (const S *)m, (S *)y, rows_per_part, (S *)slabs, s_begin, s_end);
-    else
-        hipLaunchKernelGGL((k_grid_normal<S, E, NS, K, DEPTH, false>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, op->dev_blocks, op->nrow,
-                           n_scalars, (const S *)m, (S *)y, rows_per_part, (S *)slabs, s_begin, s_end);
+    const bool nt = jh_stream_nt((double)op->nrow * (double)K * (double)p.n_scalars * sizeof(S));   // (a range too: the whole pass's bytes)
+    if (p.ranged) c.last_grid_range_shape = (nt ? 1 : 0) | (p.parts > 1 ? 2 : 0);
+    auto launch = [&](auto k, auto... table) {
+        hipLaunchKernelGGL(k.k, dim3((unsigned)p.gx, (unsigned)p.parts), dim3(k.blk), 0, c.stream, op->dev_blocks, table..., op->nrow, p.n_scalars, (const S *)m,
+                           (S *)y, p.rows_per_part, slabs, p.s_begin, p.s_end);
+    };
+    // (the packed table for grids of plain diagonals too: within the noise of this kernel, profiles/bench_grid_normal_r06.txt)
+    if (!op->all_diag) launch(pick_grid_normal<S, E, NS, K, true>(nt), (const uint64_t *)op->grid_words);
+    else launch(pick_grid_normal<S, E, NS, K, false>(nt));
     JH_CHECK_HIP(hipGetLastError());
-    if (parts > 1 && !ranged) return jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, (int64_t)K * n_scalars, parts, y, 0, (int64_t)K * n_scalars);
-    if (parts > 1)                                             // (the slabs keep the whole block's stride: the range of each piece)
-        for (int k = 0; k < K; k++)
-            JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, (const S *)slabs + (int64_t)k * n_scalars + s_begin, (int64_t)K * n_scalars, parts, y,
-                                   (int64_t)k * n_scalars + s_begin, (int64_t)k * n_scalars + s_end));
-    return JH_OK;
-}
-
-template <typename S, int E, int NS>
-int grid_normal_k(const jh_blockop *op, void *y, const void *m, int64_t first_elem, int64_t end_elem)
-{
-    // rows in flight: K x DEPTH = 8 (6 for K = 3) coefficient packs per lane; 12 / 9 / 12 measured 2-3 % slower for K = 2 / 4 and within the noise for
-    // K = 3 (profiles/bench_grid_normal_r06.txt)
-    switch (op->ncol) {
-    case 2: return launch_grid_normal<S, E, NS, 2, 4>(op, y, m, first_elem, end_elem);
-    case 3: return launch_grid_normal<S, E, NS, 3, 2>(op, y, m, first_elem, end_elem);
-    default: return launch_grid_normal<S, E, NS, 4, 2>(op, y, m, first_elem, end_elem);
-    }
+    return grid_fold(p, K, slabs, y);
 }
 
 }  // namespace
@@ -262,8 +245,7 @@ bool grid_normal_ok(const jh_blockop *op, const void *y, const void *m)
 {
     const int64_t knob = jh_ctx().grid_normal;
     if (knob == 0 || !grid_shape_ok(op, knob != 2)) return false;
-    const size_t es = jh_dtype_size(op->dtype), sa = jh_dtype_complex(op->dtype) ? es / 2 : es;
-    return ((((uintptr_t)y) | ((uintptr_t)m)) & (sa - 1)) == 0;
+    return vectors_scalar_aligned(op->dtype, y, m);
 }
 
 int grid_words_ensure(const jh_blockop *op)
@@ -294,7 +276,7 @@ static int grid_normal_by_dtype(const jh_blockop *op, void *y, const void *m, in
     JH_TRY(grid_words_ensure(op));                            // the packed table of a mixed grid, row-major (N x K words), built on first use
     return jh_by_dtype(op->dtype, "grid_normal", [&](auto t) {
         using T = decltype(t);
-        return grid_normal_k<typename T::S, T::E, T::NS>(op, y, m, first_elem, end_elem);
+        return grid_by_k(op->ncol, [&](auto k) { return launch_grid_normal<typename T::S, T::E, T::NS, decltype(k)::value>(op, y, m, first_elem, end_elem); });
     });
 }
 

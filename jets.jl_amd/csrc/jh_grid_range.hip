@@ -104,55 +104,40 @@ __global__ __launch_bounds__(256) void k_grid_adj(const jh_dev_block *__restrict
     for (int k = 0; k < K; k++) st_pack<false, S, NS>(o + (int64_t)k * n_scalars, s0, sk, acc[k]);
 }
 
-template <typename S, int E, int NS, int K, int DEPTH>
+// rows in flight: the depths of k_grid_normal -- K x DEPTH = 8 (6 for K = 3) coefficient packs per lane, plus DEPTH packs of d
+template <int K> struct grid_adj_depth { static constexpr int value = K == 2 ? 4 : 2; };
+
+template <typename S, int E, int NS, int K> struct GridAdjPicker {
+    static constexpr int D = grid_adj_depth<K>::value;
+    using Kernel = decltype(&k_grid_adj<S, E, NS, K, D, false, false>);
+    bool nt, mixed;
+    Picked<Kernel> got;
+    template <bool NTV, bool MIX> bool row()
+    {
+        if (nt == NTV && mixed == MIX) got = {&k_grid_adj<S, E, NS, K, D, NTV, MIX>, 256, 1, D};
+        return got.k != nullptr;
+    }
+    Picked<Kernel> pick() { (void)(row<false, false>() || row<true, false>() || row<false, true>() || row<true, true>()); return got; }
+};
+
+// (end_elem >= 0: the adjoint is only ever ranged)
+template <typename S, int E, int NS, int K>
 int launch_grid_adj(const jh_blockop *op, void *m, const void *d, int64_t first_elem, int64_t end_elem)
 {
     jh_context &c = jh_ctx();
-    const int64_t n_scalars = op->row_len[0] * E, s_begin = first_elem * E, s_end = end_elem * E;
-    const int64_t packs = (s_end - s_begin + NS - 1) / NS;
-    const int64_t gx = (packs + 255) / 256;
-    // the part rules of launch_grid_normal, over the range's workgroups (a range shorter than one pack loads from before s_begin: one part)
-    int64_t parts = s_end - s_begin < NS ? 1 : jhb::pick_adj_parts(gx, op->nrow), rows_per_part = 0;
-    if (parts == 1 && s_end - s_begin >= NS && c.adj_split < 0 && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
-    void *slabs = nullptr;
-    if (parts > 1) {
-        rows_per_part = (op->nrow + parts - 1) / parts;
-        parts = (op->nrow + rows_per_part - 1) / rows_per_part;
-        JH_TRY(jhb::split_slabs(m, (size_t)parts * (size_t)K * (size_t)n_scalars * sizeof(S), &slabs));
-    }
-    c.last_adj_parts = parts;
+    const GridPlan p = grid_plan(op, E, NS, first_elem, end_elem);
+    S *slabs = nullptr;
+    JH_TRY(grid_slabs(p, K, m, &slabs));
+    c.last_adj_parts = p.parts;
     c.last_adj_launches = 1;
     // streamed once per pass: the coefficients and d -- over the WHOLE adjoint's bytes, so that a range streams like the whole vector would
-    const bool nt = jh_stream_nt(((double)K + 1.0) * (double)op->nrow * (double)n_scalars * sizeof(S));
-    c.last_grid_range_shape = (nt ? 1 : 0) | (parts > 1 ? 2 : 0);
-#define JH_GRID_ADJ(NTV, MIX)                                                                                                                      \
-    hipLaunchKernelGGL((k_grid_adj<S, E, NS, K, DEPTH, NTV, MIX>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, op->dev_blocks,    \
-                       (const uint64_t *)op->grid_words, op->nrow, n_scalars, (const S *)d, (S *)m, rows_per_part, (S *)slabs, s_begin, s_end)
-    if (!op->all_diag) {
-        if (nt) JH_GRID_ADJ(true, true);
-        else JH_GRID_ADJ(false, true);
-    } else {
-        if (nt) JH_GRID_ADJ(true, false);
-        else JH_GRID_ADJ(false, false);
-    }
-#undef JH_GRID_ADJ
+    const bool nt = jh_stream_nt(((double)K + 1.0) * (double)op->nrow * (double)p.n_scalars * sizeof(S));
+    c.last_grid_range_shape = (nt ? 1 : 0) | (p.parts > 1 ? 2 : 0);
+    const auto k = GridAdjPicker<S, E, NS, K>{nt, !op->all_diag, {}}.pick();
+    hipLaunchKernelGGL(k.k, dim3((unsigned)p.gx, (unsigned)p.parts), dim3(k.blk), 0, c.stream, op->dev_blocks, (const uint64_t *)op->grid_words, op->nrow,
+                       p.n_scalars, (const S *)d, (S *)m, p.rows_per_part, slabs, p.s_begin, p.s_end);
     JH_CHECK_HIP(hipGetLastError());
-    if (parts > 1)                                             // (the slabs keep the whole block's stride: the range of each piece)
-        for (int k = 0; k < K; k++)
-            JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, (const S *)slabs + (int64_t)k * n_scalars + s_begin, (int64_t)K * n_scalars, parts, m,
-                                   (int64_t)k * n_scalars + s_begin, (int64_t)k * n_scalars + s_end));
-    return JH_OK;
-}
-
-template <typename S, int E, int NS>
-int grid_adj_k(const jh_blockop *op, void *m, const void *d, int64_t first_elem, int64_t end_elem)
-{
-    // rows in flight: the depths of k_grid_normal -- K x DEPTH = 8 (6 for K = 3) coefficient packs per lane, plus DEPTH packs of d
-    switch (op->ncol) {
-    case 2: return launch_grid_adj<S, E, NS, 2, 4>(op, m, d, first_elem, end_elem);
-    case 3: return launch_grid_adj<S, E, NS, 3, 2>(op, m, d, first_elem, end_elem);
-    default: return launch_grid_adj<S, E, NS, 4, 2>(op, m, d, first_elem, end_elem);
-    }
+    return grid_fold(p, K, slabs, m);
 }
 
 }  // namespace
@@ -164,8 +149,7 @@ namespace jhb {
 bool grid_range_ok(const jh_blockop *op, const void *a, const void *b, const void *c)
 {
     if (jh_ctx().grid_range != 1 || !grid_shape_ok(op, true)) return false;
-    const size_t es = jh_dtype_size(op->dtype), sa = jh_dtype_complex(op->dtype) ? es / 2 : es;
-    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & (sa - 1)) == 0;
+    return vectors_scalar_aligned(op->dtype, a, b, c);
 }
 
 int grid_range_bounds(const jh_blockop *op, int64_t first_elem, int64_t count, const char *who)
@@ -184,7 +168,7 @@ int grid_adj_range(const jh_blockop *op, void *m, const void *d, int64_t first_e
     JH_TRY(grid_words_ensure(op));
     return jh_by_dtype(op->dtype, "grid adjoint", [&](auto t) {
         using T = decltype(t);
-        return grid_adj_k<typename T::S, T::E, T::NS>(op, m, d, first_elem, first_elem + count);
+        return grid_by_k(op->ncol, [&](auto k) { return launch_grid_adj<typename T::S, T::E, T::NS, decltype(k)::value>(op, m, d, first_elem, first_elem + count); });
     });
 }
 

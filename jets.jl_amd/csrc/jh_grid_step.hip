@@ -179,69 +179,50 @@ __global__ __launch_bounds__(256) void k_grid_step(const jh_dev_block *__restric
     wg_sum_store<256>(nrm, partials + blockIdx.x + (size_t)blockIdx.y * gridDim.x);     // by (part, tile): a fixed fold order
 }
 
-template <typename S, int E, int NS, int K, int DEPTH, int MDEPTH>
+// rows in flight: plain diagonals keep the depths of k_grid_normal -- K x DEPTH = 8 (6 for K = 3) coefficient packs per lane, plus DEPTH packs
+// of u; grids of several kinds half of that for K = 2 and 4 (MDEPTH): at the plain depths their walk spills SGPRs (the block words, the scalars).
+// ComplexF32 (the longest product code) also takes one row at a time for K = 3 of several kinds and K = 4 of plain diagonals: 2 SGPRs spilled otherwise
+template <typename S, int E, int K, bool MIX> struct grid_step_depth {
+    static constexpr bool c32 = E == 2 && sizeof(S) == 4;
+    static constexpr int DEPTH = K == 2 ? 4 : (K == 3 ? 2 : (c32 ? 1 : 2)), MDEPTH = K == 2 ? 2 : (K == 3 ? (c32 ? 1 : 2) : 1);
+    static constexpr int value = MIX ? MDEPTH : DEPTH;
+};
+
+// first match of (nontemporal, several kinds, u read: beta != 0)
+template <typename S, int E, int NS, int K> struct GridStepPicker {
+    using Kernel = decltype(&k_grid_step<S, E, NS, K, 1, false, false, false>);
+    bool nt, mixed, old;
+    Picked<Kernel> got;
+    template <bool NTV, bool MIX, bool OLDV> bool row()
+    {
+        constexpr int D = grid_step_depth<S, E, K, MIX>::value;
+        if (nt == NTV && mixed == MIX && old == OLDV) got = {&k_grid_step<S, E, NS, K, D, NTV, MIX, OLDV>, 256, 1, D};
+        return got.k != nullptr;
+    }
+    template <bool MIX, bool OLDV> bool rows() { return row<false, MIX, OLDV>() || row<true, MIX, OLDV>(); }
+    Picked<Kernel> pick() { (void)(rows<false, false>() || rows<false, true>() || rows<true, false>() || rows<true, true>()); return got; }
+};
+
+// end_elem < 0: the whole block; else the positions [first_elem, end_elem) of every block, ||u||^2 deferred
+template <typename S, int E, int NS, int K>
 int launch_grid_step(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq, int64_t first_elem, int64_t end_elem)
 {
     jh_context &c = jh_ctx();
-    // end_elem < 0: the whole block; else the positions [first_elem, end_elem) of every block, launched as a vector of its own length, ||u||^2 deferred
-    // (the split walk's slabs keep the whole block's stride for a range too -- parts x K x n_scalars, of which a range touches its share: the kernel then
-    // needs no second stride; the split walk is the regime of small blocks, where that is little memory)
-    const bool ranged = end_elem >= 0;
-    const int64_t n_scalars = op->row_len[0] * E, s_begin = ranged ? first_elem * E : 0, s_end = ranged ? end_elem * E : n_scalars;
-    const int64_t packs = (s_end - s_begin + NS - 1) / NS;
-    const int64_t gx = (packs + 255) / 256;
-    int64_t parts = s_end - s_begin < NS ? 1 : jhb::pick_adj_parts(gx, op->nrow), rows_per_part = 0;   // (a range shorter than one pack loads from before s_begin: one part)
-    if (parts == 1 && s_end - s_begin >= NS && c.adj_split < 0 && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;   // (as launch_grid_normal)
-    void *slabs = nullptr;
-    if (parts > 1) {
-        rows_per_part = (op->nrow + parts - 1) / parts;
-        parts = (op->nrow + rows_per_part - 1) / rows_per_part;
-        JH_TRY(jhb::split_slabs(w, (size_t)parts * (size_t)K * (size_t)n_scalars * sizeof(S), &slabs));
-    }
-    JH_TRY(jh_ensure_partials(gx * parts));
+    const GridPlan p = grid_plan(op, E, NS, first_elem, end_elem);
+    S *slabs = nullptr;
+    JH_TRY(grid_slabs(p, K, w, &slabs));
+    JH_TRY(jh_ensure_partials(p.gx * p.parts));
     // streamed per pass: the coefficients, and u -- written, and read as well when beta != 0
-    const bool nt = jh_stream_nt(((double)K + (beta != 0.0 ? 2.0 : 1.0)) * (double)op->nrow * (double)n_scalars * sizeof(S));
-    c.last_adj_parts = parts;
+    const bool nt = jh_stream_nt(((double)K + (beta != 0.0 ? 2.0 : 1.0)) * (double)op->nrow * (double)p.n_scalars * sizeof(S));
+    c.last_adj_parts = p.parts;
     c.last_adj_launches = 1;
-    (ranged ? c.last_grid_range_shape : c.last_grid_step_shape) = (nt ? 1 : 0) | (parts > 1 ? 2 : 0);
-    const bool mixed = !op->all_diag;
-#define JH_GRID_STEP(NTV, MIX, OLDV)                                                                                                         \
-    hipLaunchKernelGGL((k_grid_step<S, E, NS, K, MIX ? MDEPTH : DEPTH, NTV, MIX, OLDV>), dim3((unsigned)gx, (unsigned)parts), dim3(256), 0, c.stream, \
-                       op->dev_blocks, (const uint64_t *)op->grid_words, op->nrow, n_scalars, (S *)u, (const S *)v, (S *)w, (S)alpha, (S)beta,    \
-                       c.part_dev, rows_per_part, (S *)slabs, s_begin, s_end)
-#define JH_GRID_STEP_OLD(NTV, MIX)         \
-    if (beta != 0.0) JH_GRID_STEP(NTV, MIX, true); \
-    else JH_GRID_STEP(NTV, MIX, false)
-    if (mixed) {
-        if (nt) JH_GRID_STEP_OLD(true, true);
-        else JH_GRID_STEP_OLD(false, true);
-    } else {
-        if (nt) JH_GRID_STEP_OLD(true, false);
-        else JH_GRID_STEP_OLD(false, false);
-    }
-#undef JH_GRID_STEP_OLD
-#undef JH_GRID_STEP
+    (p.ranged ? c.last_grid_range_shape : c.last_grid_step_shape) = (nt ? 1 : 0) | (p.parts > 1 ? 2 : 0);
+    const auto k = GridStepPicker<S, E, NS, K>{nt, !op->all_diag, beta != 0.0, {}}.pick();
+    hipLaunchKernelGGL(k.k, dim3((unsigned)p.gx, (unsigned)p.parts), dim3(k.blk), 0, c.stream, op->dev_blocks, (const uint64_t *)op->grid_words, op->nrow,
+                       p.n_scalars, (S *)u, (const S *)v, (S *)w, (S)alpha, (S)beta, c.part_dev, p.rows_per_part, slabs, p.s_begin, p.s_end);
     JH_CHECK_HIP(hipGetLastError());
-    if (parts > 1 && !ranged) JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, (int64_t)K * n_scalars, parts, w, 0, (int64_t)K * n_scalars));
-    if (parts > 1 && ranged)                                                        // (the slabs keep the whole block's stride: the range of each piece)
-        for (int k = 0; k < K; k++)
-            JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, (const S *)slabs + (int64_t)k * n_scalars + s_begin, (int64_t)K * n_scalars, parts, w,
-                                   (int64_t)k * n_scalars + s_begin, (int64_t)k * n_scalars + s_end));
-    return jhb::step_finish_normsq(gx * parts, normsq, ranged);
-}
-
-template <typename S, int E, int NS>
-int grid_step_k(const jh_blockop *op, void *u, const void *v, void *w, double alpha, double beta, double *normsq, int64_t first_elem, int64_t end_elem)
-{
-    // rows in flight: plain diagonals keep the depths of k_grid_normal -- K x DEPTH = 8 (6 for K = 3) coefficient packs per lane, plus DEPTH packs
-    // of u; grids of several kinds half of that for K = 2 and 4 (MDEPTH): at the plain depths their walk spills SGPRs (the block words, the scalars).
-    // ComplexF32 (the longest product code) also takes one row at a time for K = 3 of several kinds and K = 4 of plain diagonals: 2 SGPRs spilled otherwise
-    constexpr bool c32 = E == 2 && sizeof(S) == 4;
-    switch (op->ncol) {
-    case 2: return launch_grid_step<S, E, NS, 2, 4, 2>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
-    case 3: return launch_grid_step<S, E, NS, 3, 2, c32 ? 1 : 2>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
-    default: return launch_grid_step<S, E, NS, 4, c32 ? 1 : 2, 1>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
-    }
+    JH_TRY(grid_fold(p, K, slabs, w));
+    return jhb::step_finish_normsq(p.gx * p.parts, normsq, p.ranged);
 }
 
 }  // namespace
@@ -251,8 +232,7 @@ namespace jhb {
 bool grid_step_ok(const jh_blockop *op, const void *u, const void *v, const void *w)
 {
     if (jh_ctx().grid_step == 0 || !grid_shape_ok(op, true)) return false;
-    const size_t es = jh_dtype_size(op->dtype), sa = jh_dtype_complex(op->dtype) ? es / 2 : es;
-    return ((((uintptr_t)u) | ((uintptr_t)v) | ((uintptr_t)w)) & (sa - 1)) == 0;
+    return vectors_scalar_aligned(op->dtype, u, v, w);
 }
 
 // the caller has checked grid_step_ok; w must not alias v (jh_blockop_bidiag_step)
@@ -261,7 +241,9 @@ static int grid_step_by_dtype(const jh_blockop *op, void *u, const void *v, void
     JH_TRY(grid_words_ensure(op));
     return jh_by_dtype(op->dtype, "grid step", [&](auto t) {
         using T = decltype(t);
-        return grid_step_k<typename T::S, T::E, T::NS>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
+        return grid_by_k(op->ncol, [&](auto k) {
+            return launch_grid_step<typename T::S, T::E, T::NS, decltype(k)::value>(op, u, v, w, alpha, beta, normsq, first_elem, end_elem);
+        });
     });
 }
 

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <atomic>
+#include <type_traits>
 #include <vector>
 #include "../../include/jetship.h"
 
@@ -175,6 +176,16 @@ template <class F> inline int jh_by_dtype(int dtype, const char *who, F &&f)
     case JH_C32: return f(jh_elem<float, 2, 4>{});
     case JH_C64: return f(jh_elem<double, 2, 2>{});
     default: return jh_fail(JH_ERR_INVALID, "%s: unknown dtype %d", who, dtype);
+    }
+}
+// The block columns K = 2 .. 4 of an N x K grid as a constant: grid_by_k(ncol, f) calls f(k) with `decltype(k)::value` == K (the caller has checked
+// grid_shape_ok: nothing else arrives) and returns what f returns.
+template <class F> inline int grid_by_k(int64_t ncol, F &&f)
+{
+    switch (ncol) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
     }
 }
 

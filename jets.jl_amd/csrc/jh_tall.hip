@@ -582,6 +582,21 @@ int64_t pick_adj_parts(int64_t gx, int64_t nrow)
     if (parts > 65535) parts = 65535;                                    // gridDim.y
     return parts < 2 ? 1 : parts;
 }
+
+// The part rule of the one-pass grid kernels and the tall chains (the tall walks below have no bump to two parts, and `direct` / `from_found` rules of their
+// own).  A range shorter than one pack loads from before its begin: one part.  Else pick_adj_parts, or two parts
+// (one workgroup per CU, up to two: the ordered walk is latency-bound there.  Measured on the TALL chains, whose three or four streams per row show it --
+// 4096 x 64^3, 256 workgroups: A' o W o A 4.37 TB/s in one part, 7.04 in two, 6.3 in four or more; profiles/bench_chains_r06_split.txt; the grid kernels took the rule over unmeasured).
+// The part count is then re-derived from the rows per part, so that no part is empty.
+RowParts pick_row_parts(int64_t span, int NS, int64_t gx, int64_t nrow)
+{
+    jh_context &c = jh_ctx();
+    int64_t parts = span < NS ? 1 : pick_adj_parts(gx, nrow);
+    if (parts == 1 && span >= NS && c.adj_split < 0 && nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
+    if (parts == 1) return {1, nrow};
+    const int64_t rows_per_part = (nrow + parts - 1) / parts;
+    return {(nrow + rows_per_part - 1) / rows_per_part, rows_per_part};
+}
 }  // namespace jhb
 namespace {
 

@@ -488,6 +488,20 @@ struct jh_chain {
 
 namespace {
 
+// the FORWARD chain's instantiations of one workgroup size: first match of (nontemporal, range-side coefficient streams)
+template <typename S, int E, int NS, int BLK> struct ChainFwdPicker {
+    using Kernel = decltype(&k_chain_fwd<S, E, NS, false, BLK, 0>);
+    bool nt;
+    int nw;
+    Picked<Kernel> got;
+    template <bool NTV, int NWV> bool row()
+    {
+        if (nt == NTV && nw == NWV) got = {&k_chain_fwd<S, E, NS, NTV, BLK, NWV>, BLK, 1, 0};
+        return got.k != nullptr;
+    }
+    Picked<Kernel> pick() { (void)(row<false, 0>() || row<true, 0>() || row<false, 1>() || row<true, 1>() || row<false, 2>() || row<true, 2>()); return got; }
+};
+
 template <typename S, int E, int NS>
 int launch_chain_fwd(const jh_chain *ch, void *d, const void *m, int64_t n_scalars, int accumulate)
 {
@@ -505,15 +519,10 @@ int launch_chain_fwd(const jh_chain *ch, void *d, const void *m, int64_t n_scala
     if (ctiles > gx) ctiles = gx;
     const bool off_grid = row_bytes % 16 != 0 || !op->coeff_aligned16 || !ch->coeff16 || ((((uintptr_t)d) | ((uintptr_t)m)) & 15u) != 0;
     const bool nt = jh_stream_nt(ch->stream_bytes + (double)op->nrow * (double)row_bytes) && !(c.ua_nt == 0 || (c.ua_nt < 0 && off_grid));
-#define JH_CHAIN_FWD(NTV, NWV)                                                                                                              \
-    hipLaunchKernelGGL((k_chain_fwd<S, E, NS, NTV, BLK, NWV>), dim3((unsigned)(gx * gy)), dim3(BLK), 0, c.stream, op->dev_blocks, op->nrow, (int)G, \
-                       ch->args, (const S *)m, (S *)d, n_scalars, (unsigned)gx, (unsigned)gy, (unsigned)ctiles, accumulate)
-    switch (ch->nw) {
-    case 0: if (nt) JH_CHAIN_FWD(true, 0); else JH_CHAIN_FWD(false, 0); break;
-    case 1: if (nt) JH_CHAIN_FWD(true, 1); else JH_CHAIN_FWD(false, 1); break;
-    default: if (nt) JH_CHAIN_FWD(true, 2); else JH_CHAIN_FWD(false, 2); break;
-    }
-#undef JH_CHAIN_FWD
+    const auto k = ChainFwdPicker<S, E, NS, BLK>{nt, ch->nw < 2 ? ch->nw : 2, {}}.pick();
+    JH_REQUIRE(k.k && k.blk == BLK, "chain forward: no kernel for %d range-side streams", ch->nw);   // (gx above: BLK lanes of one pack)
+    hipLaunchKernelGGL(k.k, dim3((unsigned)(gx * gy)), dim3(k.blk), 0, c.stream, op->dev_blocks, op->nrow, (int)G, ch->args, (const S *)m, (S *)d, n_scalars,
+                       (unsigned)gx, (unsigned)gy, (unsigned)ctiles, accumulate);
     JH_CHECK_HIP(hipGetLastError());
     return JH_OK;
 }
@@ -530,6 +539,39 @@ struct ChainStep {
     double alpha = 1.0, beta = 0.0;
     double *normsq = nullptr;
     bool defer = false;                      // a ranged step (jh_chain_bidiag_step_range) with normsq NULL: its share joins the deferred accumulator
+};
+
+// the instantiations of one mode: first match of (shape: workgroup x packs per lane x rows in flight; nontemporal; range-side coefficient streams)
+template <typename S, int E, int NS, int MODE> struct ChainAdjPicker {
+    using Kernel = decltype(&k_chain_adj<S, E, NS, 1, 4, false, MODE, 256, 0>);
+    int shape, nw;
+    bool nt;
+    Picked<Kernel> got;
+    template <int BLK, int U, int D, bool NTV, int NWV> bool row()
+    {
+        if (nt == NTV && nw == NWV) got = {&k_chain_adj<S, E, NS, U, D, NTV, MODE, BLK, NWV>, BLK, U, D};
+        return got.k != nullptr;
+    }
+    template <int SHAPE, int BLK, int U, int D> bool rows()
+    {
+        return shape == SHAPE && (row<BLK, U, D, false, 0>() || row<BLK, U, D, true, 0>() || row<BLK, U, D, false, 1>() || row<BLK, U, D, true, 1>() ||
+                                  row<BLK, U, D, false, 2>() || row<BLK, U, D, true, 2>());
+    }
+    Picked<Kernel> pick()
+    {
+        // (rows of a few hundred KiB at most, one workgroup per CU or fewer: eight rows in flight instead of four bought nothing -- 4096 x 64^3 3.79 -> 3.73
+        // TB/s -- and their sixteen row records pushed the SGPR spills past what fits the lanes of the spill registers)
+        if constexpr (MODE == 2) {
+            // (the step holds u's packs and the update beside the adjoint's state: half the rows in flight keeps the SGPR spills of the family's
+            // census and the fat shape out of scratch)
+            bool hit = rows<0, 256, 1, 2>() || rows<1, 512, 2, 1>();
+            if constexpr (!(E == 2 && sizeof(S) == 4)) hit = hit || rows<2, 512, 4, 1>();   // (ComplexF32: the launcher caps shape 2 before it sizes the grid)
+            (void)hit;
+        } else {
+            (void)(rows<0, 256, 1, 4>() || rows<1, 512, 2, 2>() || rows<2, 512, 4, 2>());
+        }
+        return got;
+    }
 };
 
 // `ca`: the handle's own program, or one derived from it (the ADJOINT / NORMAL / step programs of a FORWARD chain: jh_tall_chain.hip)
@@ -559,18 +601,13 @@ int launch_chain_adj(const jh_chain *ch, const ChainArgs &ca, void *out, const v
     if (MODE == 2 && E == 2 && sizeof(S) == 4 && shape == 2) shape = 1;
     const int64_t per_wg = per_wg_of[shape];
     const int64_t gx = (packs + per_wg - 1) / per_wg;
-    // many rows of small blocks: the split-row walk (jh_tall.hip: pick_adj_parts; adj_split = 0 keeps the ordered, bit-exact walk) -- parts of the row sum into
+    // many rows of small blocks: the split-row walk (jh_tall.hip: pick_row_parts; adj_split = 0 keeps the ordered, bit-exact walk) -- parts of the row sum into
     // slabs of the scratch buffer, the fold of k_fold_parts, then the stages after A' and the accumulation on the folded vector (k_chain_finish; folded
     // straight into `out` when there is neither).  Tolerance parity, like every split walk.
-    int64_t parts = span < NS ? 1 : jhb::pick_adj_parts(gx, op->nrow), rows_per_part = 0;   // (a range shorter than one pack loads from before s_begin: one part)
-    // (one workgroup per CU, up to two: the chain's three or four streams per row leave the ordered walk latency-bound there -- 4096 x 64^3, 256 workgroups:
-    // A' o W o A 4.37 TB/s in one part, 7.04 in two, 6.3 in four or more; profiles/bench_chains_r06_split.txt)
-    if (parts == 1 && c.adj_split < 0 && span >= NS && op->nrow >= 256 && gx < 2 * (int64_t)c.cu_count) parts = 2;
+    const auto [parts, rows_per_part] = jhb::pick_row_parts(span, NS, gx, op->nrow);
     const bool finish = accumulate != 0 || (ca.post.st[0] & 15u) != CK_NONE;
     S *slabs = nullptr, *folded = (S *)out;
     if (parts > 1) {
-        rows_per_part = (op->nrow + parts - 1) / parts;
-        parts = (op->nrow + rows_per_part - 1) / rows_per_part;
         void *sp = nullptr;
         JH_TRY(jhb::split_slabs(out, (size_t)(parts + (finish ? 1 : 0)) * (size_t)span * sizeof(S), &sp));
         slabs = (S *)sp;
@@ -585,33 +622,11 @@ int launch_chain_adj(const jh_chain *ch, const ChainArgs &ca, void *out, const v
         beta = (S)step->beta;
     }
     double *partials = MODE == 2 ? c.part_dev : nullptr;
-#define JH_CHAIN_ADJ(BLKV, UV, DV, NTV, NWV)                                                                                                 \
-    hipLaunchKernelGGL((k_chain_adj<S, E, NS, UV, DV, NTV, MODE, BLKV, NWV>), dim3((unsigned)gx, (unsigned)parts), dim3(BLKV), 0, c.stream, op->dev_blocks, \
-                       op->nrow, ca, (S *)out, (const S *)in, n_scalars, s_begin, s_end, accumulate, rows_per_part, slabs, u, alpha, beta, partials)
-#define JH_CHAIN_ADJ_NW(BLKV, UV, DV, NTV)                                                                                                    \
-    switch (ch->nw) {                                                                                                                      \
-    case 0: JH_CHAIN_ADJ(BLKV, UV, DV, NTV, 0); break;                                                                                     \
-    case 1: JH_CHAIN_ADJ(BLKV, UV, DV, NTV, 1); break;                                                                                     \
-    default: JH_CHAIN_ADJ(BLKV, UV, DV, NTV, 2); break;                                                                                    \
-    }
-#define JH_CHAIN_ADJ_SHAPE(NTV)                                                                                                              \
-    /* (rows of a few hundred KiB at most, one workgroup per CU or fewer: eight rows in flight instead of four bought nothing -- 4096 x 64^3 3.79 -> 3.73   \
-       TB/s -- and their sixteen row records pushed the SGPR spills past what fits the lanes of the spill registers) */                             \
-    if constexpr (MODE == 2) {                                                                                                             \
-        /* (the step holds u's packs and the update beside the adjoint's state: half the rows in flight keeps the SGPR spills of the family's   \
-           census and the fat shape out of scratch) */                                                                                     \
-        if (shape == 0) { JH_CHAIN_ADJ_NW(256, 1, 2, NTV) }                                                                                \
-        else if (shape == 1) { JH_CHAIN_ADJ_NW(512, 2, 1, NTV) }                                                                           \
-        else if constexpr (!(E == 2 && sizeof(S) == 4)) { JH_CHAIN_ADJ_NW(512, 4, 1, NTV) }   /* (ComplexF32: shape 2 was capped above) */ \
-    } else {                                                                                                                               \
-        if (shape == 0) { JH_CHAIN_ADJ_NW(256, 1, 4, NTV) }                                                                                \
-        else if (shape == 1) { JH_CHAIN_ADJ_NW(512, 2, 2, NTV) }                                                                           \
-        else { JH_CHAIN_ADJ_NW(512, 4, 2, NTV) }                                                                                           \
-    }
-    if (nt) { JH_CHAIN_ADJ_SHAPE(true) } else { JH_CHAIN_ADJ_SHAPE(false) }
-#undef JH_CHAIN_ADJ_SHAPE
-#undef JH_CHAIN_ADJ_NW
-#undef JH_CHAIN_ADJ
+    const auto k = ChainAdjPicker<S, E, NS, MODE>{shape, ch->nw < 2 ? ch->nw : 2, nt, {}}.pick();
+    JH_REQUIRE(k.k && (int64_t)k.blk * k.u == per_wg, "chain %d: picked %d x %d for a grid sized for %lld packs per workgroup (shape %d, %d range-side streams)",
+               MODE, k.blk, k.u, (long long)per_wg, shape, ch->nw);
+    hipLaunchKernelGGL(k.k, dim3((unsigned)gx, (unsigned)parts), dim3(k.blk), 0, c.stream, op->dev_blocks, op->nrow, ca, (S *)out, (const S *)in, n_scalars,
+                       s_begin, s_end, accumulate, rows_per_part, slabs, u, alpha, beta, partials);
     JH_CHECK_HIP(hipGetLastError());
     if (parts > 1) {
         JH_TRY(jhb::fold_parts(sizeof(S) == 4 ? JH_F32 : JH_F64, slabs, span, parts, folded, s_begin, s_end));
