@@ -74,17 +74,30 @@ __global__ __launch_bounds__(256) void k_lsqr_fold(const double *__restrict__ pa
     wg_sum_to<256>(v, out);
 }
 
-struct Tmp {                                     // domain-sized work vectors, released on every exit path
-    jh_bvec *v = nullptr, *w = nullptr, *atu = nullptr;
-    double *parts = nullptr;                     // 2 x grid per-workgroup partials + 2 result slots
-    ~Tmp()
+// one member's domain-sized work vectors (and, LSQR: its per-workgroup partials), made in the member's context and released on every exit path
+template <int N> struct DomVecs {
+    jh_bvec *vec[N] = {};
+    double *parts = nullptr;
+    DomVecs() = default;
+    DomVecs(const DomVecs &) = delete;
+    DomVecs &operator=(const DomVecs &) = delete;
+    ~DomVecs()
     {
         if (parts) (void)hipFree(parts);
-        if (v) (void)jh_bvec_destroy(v);
-        if (w) (void)jh_bvec_destroy(w);
-        if (atu) (void)jh_bvec_destroy(atu);
+        for (jh_bvec *p : vec)
+            if (p) (void)jh_bvec_destroy(p);
+    }
+    jh_bvec *operator[](int i) const { return vec[i]; }
+    int create(int64_t n, int dtype, size_t nparts = 0)
+    {
+        const int64_t len1[1] = {n};
+        for (jh_bvec *&p : vec) JH_TRY(jh_bvec_create(1, len1, dtype, &p));
+        if (nparts) JH_CHECK_HIP(jh_device_malloc(jh_ctx().device, (void **)&parts, sizeof(double) * nparts));
+        return JH_OK;
     }
 };
+enum { V, W, ATU };                              // LSQR's three
+enum { P, S, Y };                                // CGLS's and CGNR's
 
 int lincomb1(jh_bvec *dst, double c0, const jh_bvec *x0)
 {
@@ -93,27 +106,39 @@ int lincomb1(jh_bvec *dst, double c0, const jh_bvec *x0)
     return jh_lincomb(dst, 1, coef, xs);
 }
 
-// launch helpers: a complex vector is 2n reals for these real-coefficient updates
+int lincomb2(jh_bvec *dst, double c0, const jh_bvec *x0, double c1, const jh_bvec *x1)
+{
+    const double coef[4] = {c0, 0.0, c1, 0.0};
+    const jh_bvec *v[2] = {x0, x1};
+    return jh_lincomb(dst, 2, coef, v);
+}
+
+// workgroups of the domain-side kernels: a complex vector is 2n reals for these real-coefficient updates
+int dom_grid(int64_t n, int dtype)
+{
+    const int64_t ns_dom = n * (jh_dtype_complex(dtype) ? 2 : 1);
+    const int grid = (int)((ns_dom + 255) / 256 < 4096 ? (ns_dom + 255) / 256 : 4096);
+    return grid < 1 ? 1 : grid;
+}
+
 int launch_vhat(int dtype, jh_bvec *v, const jh_bvec *atu, double c0, double c1, double *parts, int grid)
 {
-    const bool f64 = (dtype == JH_F64 || dtype == JH_C64);
-    const int64_t ns = v->length * (jh_dtype_complex(dtype) ? 2 : 1);
-    hipStream_t st = jh_ctx().stream;
-    if (f64) hipLaunchKernelGGL((k_lsqr_vhat<double>), dim3(grid), dim3(256), 0, st, (double *)v->data, (const double *)atu->data, ns, c0, c1, parts);
-    else hipLaunchKernelGGL((k_lsqr_vhat<float>), dim3(grid), dim3(256), 0, st, (float *)v->data, (const float *)atu->data, ns, (float)c0, (float)c1, parts);
-    JH_CHECK_HIP(hipGetLastError());
-    return JH_OK;
+    return jh_by_dtype(dtype, "lsqr v update", [&](auto t) -> int {
+        using T = typename decltype(t)::S;
+        hipLaunchKernelGGL((k_lsqr_vhat<T>), dim3(grid), dim3(256), 0, jh_ctx().stream, (T *)v->data, (const T *)atu->data, v->length * decltype(t)::E, (T)c0, (T)c1, parts);
+        JH_CHECK_HIP(hipGetLastError());
+        return JH_OK;
+    });
 }
 
 int launch_xw(int dtype, jh_bvec *v, jh_bvec *x, jh_bvec *w, double cv, double t1, double t2, double *parts, int grid)
 {
-    const bool f64 = (dtype == JH_F64 || dtype == JH_C64);
-    const int64_t ns = v->length * (jh_dtype_complex(dtype) ? 2 : 1);
-    hipStream_t st = jh_ctx().stream;
-    if (f64) hipLaunchKernelGGL((k_lsqr_xw<double>), dim3(grid), dim3(256), 0, st, (double *)v->data, (double *)x->data, (double *)w->data, ns, cv, t1, t2, parts);
-    else hipLaunchKernelGGL((k_lsqr_xw<float>), dim3(grid), dim3(256), 0, st, (float *)v->data, (float *)x->data, (float *)w->data, ns, (float)cv, (float)t1, (float)t2, parts);
-    JH_CHECK_HIP(hipGetLastError());
-    return JH_OK;
+    return jh_by_dtype(dtype, "lsqr x/w update", [&](auto t) -> int {
+        using T = typename decltype(t)::S;
+        hipLaunchKernelGGL((k_lsqr_xw<T>), dim3(grid), dim3(256), 0, jh_ctx().stream, (T *)v->data, (T *)x->data, (T *)w->data, v->length * decltype(t)::E, (T)cv, (T)t1, (T)t2, parts);
+        JH_CHECK_HIP(hipGetLastError());
+        return JH_OK;
+    });
 }
 
 }  // namespace
@@ -122,7 +147,7 @@ int launch_xw(int dtype, jh_bvec *v, jh_bvec *x, jh_bvec *w, double cv, double t
 // The loop below (lsqr_impl) synchronises the host twice per iteration to turn two sums into the next coefficients.  For an
 // operator whose pass takes a few hundred microseconds that costs as much as the kernels (64 x 64^3: 84 us per iteration, 35 of
 // them on the device).  Here the scalars of Paige & Saunders' recurrences are a struct in device memory, two one-thread kernels
-// update it from the sums exactly as the host code does (same operations, same order, fp64), the step / v / x-w kernels read
+// update it from the sums with the two functions the host loop calls (lsqr_s1, lsqr_s2: the recurrences exist once), the step / v / x-w kernels read
 // their coefficients from it, and a finished solve turns every kernel into a no-op -- so an iteration has fixed launch parameters,
 // is captured ONCE as a hipGraph and replayed; the host looks at the `done` flag every few iterations.  Same kernels, same
 // arithmetic: the iterates are those of lsqr_impl bit for bit.
@@ -136,7 +161,7 @@ struct LsqrDev {
 };
 
 // after the step: beta from ||u||^2, ||w|| of the previous iteration, the coefficients of the v update
-__device__ inline void lsqr_s1(LsqrDev *st, double normsq, const double *__restrict__ slot_w)
+__host__ __device__ inline void lsqr_s1(LsqrDev *st, double normsq, const double *__restrict__ slot_w)
 {
     st->itn++;
     st->beta = sqrt(normsq);
@@ -150,8 +175,8 @@ __device__ inline void lsqr_s1(LsqrDev *st, double normsq, const double *__restr
     }
 }
 
-// after the v update: alpha, the rotations, the coefficients of the x / w update, the stopping rules (lsqr_impl, line by line)
-__device__ inline void lsqr_s2(LsqrDev *st, double sum_v, double *__restrict__ history)
+// after the v update: alpha, the rotations, the coefficients of the x / w update, the norm estimates, the stopping rules
+__host__ __device__ inline void lsqr_s2(LsqrDev *st, double sum_v, double *__restrict__ history)
 {
     double alpha = st->alpha, beta = st->beta, rhobar = st->rhobar, phibar = st->phibar;
     double cv = 1.0;
@@ -162,7 +187,7 @@ __device__ inline void lsqr_s2(LsqrDev *st, double sum_v, double *__restrict__ h
     const double damp = st->damp;
     const double rhobar1 = sqrt(rhobar * rhobar + damp * damp);
     const double rho = sqrt(rhobar1 * rhobar1 + beta * beta);
-    if (!(rhobar1 > 0 && isfinite(rho))) {       // far past convergence under force_maxiter: the recurrences have underflowed
+    if (!(rhobar1 > 0 && std::isfinite(rho))) {  // far past convergence under force_maxiter: the recurrences have underflowed
         if (!st->istop) st->istop = 6;
         st->itn--;
         st->alpha = alpha;
@@ -230,6 +255,43 @@ __device__ inline void lsqr_s2(LsqrDev *st, double sum_v, double *__restrict__ h
         st->pending = 1;                         // x and w of THIS iteration are still updated
         st->halt = 1;
     }
+}
+
+// the state before the first iteration, from the start-up's alpha = ||A'u|| / beta, beta = ||u||, ||b|| and ||w||
+static LsqrDev lsqr_state_init(double alpha, double beta, double bnorm, double wnorm, double damp, double atol, double btol, double conlim, int maxiter,
+                               int force_maxiter)
+{
+    LsqrDev h{};
+    h.alpha = alpha;
+    h.beta = beta;
+    h.rhobar = alpha;
+    h.phibar = beta;
+    h.cs2 = -1.0;
+    h.bnorm = bnorm;
+    h.wnorm = wnorm;
+    h.damp = damp;
+    h.atol = atol;
+    h.btol = btol;
+    h.ctol = conlim > 0 ? 1.0 / conlim : 0.0;
+    h.r1norm = h.r2norm = beta;
+    h.arnorm = alpha * beta;
+    h.coef_step[0] = 1.0;
+    h.coef_step[1] = -alpha / beta;
+    h.maxiter = maxiter;
+    h.force = force_maxiter ? 1 : 0;
+    return h;
+}
+
+static void lsqr_result_from(const LsqrDev &h, jh_lsqr_result *res)
+{
+    res->istop = h.istop;
+    res->itn = h.itn;
+    res->r1norm = h.r1norm;
+    res->r2norm = h.r2norm;
+    res->anorm = h.anorm;
+    res->acond = h.acond;
+    res->arnorm = h.arnorm;
+    res->xnorm = h.xnorm;
 }
 
 __global__ void k_lsqr_s1(LsqrDev *st, const double *__restrict__ normsq, const double *__restrict__ slot_w)
@@ -327,6 +389,25 @@ __global__ __launch_bounds__(256) void k_lsqr_xw_dev(S *v, S *x, S *w, int64_t n
     wg_sum_to<256>(nrm, partials + blockIdx.x);
 }
 
+// the same two launches with the coefficients in device memory (no error check here: the iteration that enqueues them asks once)
+static int launch_vhat_dev(int dtype, jh_bvec *v, const jh_bvec *atu, const LsqrDev *st, double *parts, int grid)
+{
+    return jh_by_dtype(dtype, "lsqr v update", [&](auto t) -> int {
+        using T = typename decltype(t)::S;
+        hipLaunchKernelGGL((k_lsqr_vhat_dev<T>), dim3(grid), dim3(256), 0, jh_ctx().stream, (T *)v->data, (const T *)atu->data, v->length * decltype(t)::E, st, parts);
+        return JH_OK;
+    });
+}
+
+static int launch_xw_dev(int dtype, jh_bvec *v, jh_bvec *x, jh_bvec *w, const LsqrDev *st, double *parts, int grid)
+{
+    return jh_by_dtype(dtype, "lsqr x/w update", [&](auto t) -> int {
+        using T = typename decltype(t)::S;
+        hipLaunchKernelGGL((k_lsqr_xw_dev<T>), dim3(grid), dim3(256), 0, jh_ctx().stream, (T *)v->data, (T *)x->data, (T *)w->data, v->length * decltype(t)::E, st, parts);
+        return JH_OK;
+    });
+}
+
 // WHO sums across shards of the operator:
 //   none   one context holds all rows (jh_lsqr_solve);
 //   ranks  op/u are THIS rank's block rows of a row-partitioned operator and the exchange runs over the communicator of
@@ -371,229 +452,213 @@ struct Passes {
     int normal(jh_bvec *y, const jh_bvec *m) { return ch ? jhb::chain_apply_derived(ch, JH_CHAIN_NORMAL, y, m) : jh_blockop_normal_mul(op, y, m); }
 };
 
-static int lsqr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *us, jh_bvec *const *xs, int use_x0, double damp, double atol,
-                     double btol, double conlim, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history, const Exch ex,
-                     const jh_chain *ch = nullptr, const bool grid_ok = false)
-{
-    JH_REQUIRE(ops && us && xs && res && M >= 1, "jh_lsqr_solve: null argument");
-    JH_REQUIRE(maxiter >= 0, "jh_lsqr_solve: maxiter must be >= 0");
-    for (int k = 0; k < M; k++) JH_REQUIRE(ops[k] && us[k] && xs[k], "jh_lsqr_solve: null argument (member %d)", k);
-    auto use = [&](int k) { return jh_enter(ops[k], us[k], xs[k]); };
-    JH_TRY(use(0));
-    int64_t nb = 0, n = 0;
+// One solve's shards -- member k's operator, its rows of the right-hand side and its replica of x -- and the steps the three loops below take over
+// them.  `who` is the public name the messages carry.
+struct Shards {
+    const char *const who;
+    const int M;
+    const jh_blockop *const *const ops;
+    jh_bvec *const *const rhs, *const *const xs;
+    const Exch ex;
+    int64_t n = 0, chunk = 0;                    // elements of x; of an exchange range: 4 ranges, on 64 KiB boundaries
     int dtype = 0;
-    JH_TRY(jh_bvec_info(xs[0], &nb, &n, &dtype, nullptr));
-    for (int k = 0; k < M; k++) {
-        JH_REQUIRE(xs[k]->length == n && xs[k]->dtype == dtype, "jh_lsqr_solve: member %d's x differs in length or element type", k);
-        // before anything is touched: the caller can still take another path.  Rows off the 16-byte pack grid are fine (jh_blockop_tall_step_ok): the
-        // pipelined exchange cuts the DOMAIN at 16-byte bounds, and the last range may end with the vector
-        // grid_ok (jh_lsqr_solve: one GPU, unpartitioned): an N x (2 .. 4) grid of equal elementwise blocks on its one-pass step (jh_grid_step.hip)
-        const bool grid = grid_ok && !ch && M == 1 && ex == Exch::none && !jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data) &&
-                          jhb::grid_step_ok(ops[k], us[k]->data, xs[k]->data, xs[k]->data);
-        if (!ch && !grid && !jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data))
-            return jh_fail(JH_ERR_UNSUPPORTED, "jh_lsqr_solve: needs a tall operator of >= 2 equal elementwise rows");
-    }
-    std::vector<Passes> pass((size_t)M);
-    for (int k = 0; k < M; k++) { pass[k].op = ops[k]; pass[k].ch = ch; pass[k].grid = !ch && !jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data); }
-    std::vector<Tmp> t((size_t)M);
-    const int64_t len1[1] = {n};
-    const int64_t ns_dom = n * (jh_dtype_complex(dtype) ? 2 : 1);
-    int grid = (int)((ns_dom + 255) / 256 < 4096 ? (ns_dom + 255) / 256 : 4096);
-    if (grid < 1) grid = 1;
-    for (int k = 0; k < M; k++) {
-        JH_TRY(use(k));
-        JH_TRY(jh_bvec_create(1, len1, dtype, &t[k].v));
-        JH_TRY(jh_bvec_create(1, len1, dtype, &t[k].w));
-        JH_TRY(jh_bvec_create(1, len1, dtype, &t[k].atu));
-        JH_CHECK_HIP(jh_device_malloc(jh_ctx().device, (void **)&t[k].parts, sizeof(double) * (2 * (size_t)grid + 2)));
-    }
-    auto parts_v = [&](int k) { return t[k].parts; };
-    auto parts_w = [&](int k) { return t[k].parts + grid; };
-    double *slot_v = t[0].parts + 2 * grid, *slot_w = slot_v + 1;        // member 0 folds and reports the domain-side norms
-    JH_TRY(use(0));
-    jh_context &c = jh_ctx();                                            // member 0's context: its stream carries the read-backs
-    *res = jh_lsqr_result{};
-    int64_t chunk = (n + 3) / 4;                                          // exchange ranges: 4, on 64 KiB boundaries
-    chunk = (chunk + 16383) / 16384 * 16384;
+    std::vector<double> locals;                  // one scalar per member (sum)
+    Shards(const char *who_, int M_, const jh_blockop *const *ops_, jh_bvec *const *rhs_, jh_bvec *const *xs_, Exch ex_)
+        : who(who_), M(M_), ops(ops_), rhs(rhs_), xs(xs_), ex(ex_) {}
+    Shards(const Shards &) = delete;
+    Shards &operator=(const Shards &) = delete;
 
-    // sum of one scalar per member, then over the ranks
-    auto global_sum = [&](const std::vector<double> &locals, double *out) -> int {
+    int use(int k) const { return jh_enter(ops[k], rhs[k], xs[k]); }
+    // the common checks; takes(k) is the solver's own rule, asked member by member BEFORE anything is touched: the caller can still take another path
+    template <class F> int init(const jh_lsqr_result *res, int maxiter, F &&takes, const char *needs)
+    {
+        JH_REQUIRE(ops && rhs && xs && res && M >= 1, "%s: null argument", who);
+        JH_REQUIRE(maxiter >= 0, "%s: maxiter must be >= 0", who);
+        for (int k = 0; k < M; k++) JH_REQUIRE(ops[k] && rhs[k] && xs[k], "%s: null argument (member %d)", who, k);
+        JH_TRY(use(0));
+        int64_t nb = 0;
+        JH_TRY(jh_bvec_info(xs[0], &nb, &n, &dtype, nullptr));
+        for (int k = 0; k < M; k++) {
+            JH_REQUIRE(xs[k]->length == n && xs[k]->dtype == dtype, "%s: member %d's x differs in length or element type", who, k);
+            if (!takes(k)) return jh_fail(JH_ERR_UNSUPPORTED, "%s: needs %s", who, needs);
+        }
+        chunk = ((n + 3) / 4 + 16383) / 16384 * 16384;
+        locals.assign((size_t)M, 0.0);
+        return JH_OK;
+    }
+    bool tall(int k) const { return jh_blockop_tall_step_ok(ops[k], rhs[k]->data, xs[k]->data); }   // (rows off the 16-byte pack grid too)
+    // sum of one scalar per member, in index order, then over the ranks
+    int sum(const std::vector<double> &vals, double *out) const
+    {
         double s = 0.0;
-        for (double v : locals) s += v;
+        for (double v : vals) s += v;
         *out = s;
         if (ex == Exch::ranks) JH_TRY(jh_comm_allreduce_scalars(out, 1, 0));
         return JH_OK;
-    };
-    // the members' all-reduces of one collective
-    auto exchange = [&](auto &&one) -> int {
+    }
+    // the members' all-reduces of one collective: a team's as one group (the first error is kept, the group is closed all the same)
+    template <class F> int grouped(F &&one) const
+    {
         if (ex == Exch::none) return JH_OK;
         if (ex == Exch::team) { JH_TRY(use(0)); JH_TRY(jh_comm_group_begin()); }
         int st = JH_OK;
         for (int k = 0; k < M && st == JH_OK; k++) st = one(k);
         if (ex == Exch::team) { (void)use(0); const int st2 = jh_comm_group_end(); if (st == JH_OK) st = st2; }
         return st;
-    };
-    std::vector<double> locals((size_t)M);
+    }
+    template <class F> int for_ranges(F &&f) const
+    {
+        for (int64_t lo = 0; lo < n; lo += chunk) JH_TRY(f(lo, lo + chunk < n ? chunk : n - lo));
+        return JH_OK;
+    }
+    // The pipelined distributed step  rhs_k <- a*(A_k v) + b*rhs_k ; out = sum_k A_k' rhs_k ; ||rhs||^2:  every shard's rows in element ranges -- the
+    // all-reduce of a finished range of `out` runs on the exchange stream while the kernel of the next range computes; the norm accumulates on the
+    // device and is summed behind the last range: ONE host synchronisation per shard for the whole step (a team: member 0 last, whose
+    // synchronisation also lands what its stream copied before)
+    template <class FV, class FO> int ranged_step(FV &&v_of, FO &&out_of, double a, double b, double *normsq) const
+    {
+        for (int k = 0; k < M; k++) { JH_TRY(use(k)); JH_TRY(jh_normsq_reset()); }
+        JH_TRY(for_ranges([&](int64_t lo, int64_t cnt) -> int {
+            for (int k = 0; k < M; k++) JH_TRY(jh_blockop_bidiag_step_range(ops[k], rhs[k], v_of(k), out_of(k), a, b, lo, cnt, nullptr));
+            return grouped([&](int k) { return jh_comm_allreduce_sum_range(out_of(k), lo, cnt); });
+        }));
+        if (ex == Exch::ranks) return jh_comm_allreduce_normsq(normsq);
+        *normsq = 0.0;                                                   // team: the host adds the members' accumulators
+        for (int k = M - 1; k >= 0; k--) {
+            JH_TRY(use(k));
+            JH_TRY(jh_comm_join());
+            double part = 0.0;
+            JH_TRY(jh_normsq_read(&part));
+            *normsq += part;
+        }
+        return JH_OK;
+    }
+    // the members' streams have finished: the caller's temporaries may die
+    int sync_all() const
+    {
+        for (int k = 0; k < M; k++) {
+            jh_context *ck = jh_ctx_by_id(ops[k]->ctx);
+            if (ck) { JH_TRY(use(k)); JH_CHECK_HIP(hipStreamSynchronize(ck->stream)); }
+        }
+        return JH_OK;
+    }
+};
 
-    double s2 = 0.0;
-    for (int k = 0; k < M; k++) {
-        if (!use_x0) JH_TRY(jh_fill(xs[k], 0.0, 0.0));
+static std::vector<Passes> passes_of(const Shards &sh, const jh_chain *ch)
+{
+    std::vector<Passes> pass((size_t)sh.M);
+    for (int k = 0; k < sh.M; k++) { pass[k].op = sh.ops[k]; pass[k].ch = ch; pass[k].grid = !ch && !sh.tall(k); }
+    return pass;
+}
+
+// x <- 0 unless it is a warm start ;  *bsq = ||b||^2 over the shards
+static int start_norm_b(Shards &sh, int use_x0, double *bsq)
+{
+    for (int k = 0; k < sh.M; k++) {
+        if (!use_x0) JH_TRY(jh_fill(sh.xs[k], 0.0, 0.0));
         double nrm = 0.0;
-        JH_TRY(jh_norm(us[k], 2.0, &nrm));                               // ||b|| (this shard's rows)
-        locals[k] = nrm * nrm;
+        JH_TRY(jh_norm(sh.rhs[k], 2.0, &nrm));                            // ||b|| (this shard's rows)
+        sh.locals[k] = nrm * nrm;
     }
-    JH_TRY(global_sum(locals, &s2));
-    const double bnorm = std::sqrt(s2);
-    double beta = bnorm;
-    if (use_x0) {                                                        // u <- b - A x0
-        for (int k = 0; k < M; k++) JH_TRY(pass[k].fwd_axpby(us[k], xs[k], -1.0, 1.0, &locals[k]));
-        JH_TRY(global_sum(locals, &s2));
-        beta = std::sqrt(s2);
-    }
+    return sh.sum(sh.locals, bsq);
+}
+
+// ... and the residual the iterations start from, in the right-hand side's storage: rhs <- b - A x0 on a warm start ;  *rsq = ||rhs||^2
+static int start_residual(Shards &sh, std::vector<Passes> &pass, int use_x0, double *bsq, double *rsq)
+{
+    JH_TRY(start_norm_b(sh, use_x0, bsq));
+    *rsq = *bsq;
+    if (!use_x0) return JH_OK;
+    for (int k = 0; k < sh.M; k++) JH_TRY(pass[k].fwd_axpby(sh.rhs[k], sh.xs[k], -1.0, 1.0, &sh.locals[k]));
+    return sh.sum(sh.locals, rsq);
+}
+
+// LSQR's start-up: beta u = b - A x0, alpha v = A'u, w = v, and the scalar state before the first iteration
+static int lsqr_start(Shards &sh, std::vector<Passes> &pass, std::vector<DomVecs<3>> &t, int use_x0, double damp, double atol, double btol, double conlim,
+                      int maxiter, int force_maxiter, LsqrDev *h)
+{
+    const int M = sh.M;
+    double bsq = 0.0, usq = 0.0;
+    JH_TRY(start_residual(sh, pass, use_x0, &bsq, &usq));
+    const double beta = std::sqrt(usq);
     double alpha = 0.0;
     if (beta > 0) {                                                      // v = A'u / beta
-        for (int k = 0; k < M; k++) JH_TRY(pass[k].adjoint(t[k].atu, us[k]));
-        JH_TRY(exchange([&](int k) { return jh_comm_allreduce_sum(t[k].atu); }));
-        for (int k = 0; k < M; k++) JH_TRY(lincomb1(t[k].v, 1.0 / beta, t[k].atu));
-        JH_TRY(jh_norm(t[0].v, 2.0, &alpha));                            // replicas are identical: member 0 speaks for all
+        for (int k = 0; k < M; k++) JH_TRY(pass[k].adjoint(t[k][ATU], sh.rhs[k]));
+        JH_TRY(sh.grouped([&](int k) { return jh_comm_allreduce_sum(t[k][ATU]); }));
+        for (int k = 0; k < M; k++) JH_TRY(lincomb1(t[k][V], 1.0 / beta, t[k][ATU]));
+        JH_TRY(jh_norm(t[0][V], 2.0, &alpha));                           // replicas are identical: member 0 speaks for all
     } else {
-        for (int k = 0; k < M; k++) JH_TRY(jh_copy(t[k].v, xs[k]));
+        for (int k = 0; k < M; k++) JH_TRY(jh_copy(t[k][V], sh.xs[k]));
     }
     for (int k = 0; k < M; k++) {
-        if (alpha > 0) JH_TRY(lincomb1(t[k].v, 1.0 / alpha, t[k].v));
-        JH_TRY(jh_copy(t[k].w, t[k].v));
+        if (alpha > 0) JH_TRY(lincomb1(t[k][V], 1.0 / alpha, t[k][V]));
+        JH_TRY(jh_copy(t[k][W], t[k][V]));
     }
     double wnorm = 0.0;                                                  // ||w_k||, needed one iteration after w_k is written
-    JH_TRY(jh_norm(t[0].w, 2.0, &wnorm));
-    bool wnorm_pending = false;                                          // the value is in flight to member 0's red_host[5]
+    JH_TRY(jh_norm(t[0][W], 2.0, &wnorm));
+    *h = lsqr_state_init(alpha, beta, std::sqrt(bsq), wnorm, damp, atol, btol, conlim, maxiter, force_maxiter);
+    return JH_OK;
+}
 
-    double rhobar = alpha, phibar = beta, rnorm = beta, r1norm = beta, r2norm = beta, arnorm = alpha * beta;
-    double anorm = 0, acond = 0, ddnorm = 0, res2 = 0, xnorm = 0, xxnorm = 0, z = 0, cs2 = -1.0, sn2 = 0.0;
-    int itn = 0, istop = 0;
-    const double eps = 2.220446049250313e-16, ctol = conlim > 0 ? 1.0 / conlim : 0.0;
-    if (arnorm != 0) {
-        while (itn < maxiter) {
-            itn++;
+// The host-driven loop: the recurrences are lsqr_s1 / lsqr_s2 above, applied here to a host copy of the state between the launches -- two host
+// synchronisations per iteration (the step's ||u||^2, the v update's ||v||^2)
+static int lsqr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *us, jh_bvec *const *xs, int use_x0, double damp, double atol,
+                     double btol, double conlim, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history, const Exch ex,
+                     const jh_chain *ch = nullptr, const bool grid_ok = false)
+{
+    Shards sh("jh_lsqr_solve", M, ops, us, xs, ex);
+    // a chain; rows off the 16-byte pack grid are fine (jh_blockop_tall_step_ok): the pipelined exchange cuts the DOMAIN at 16-byte bounds, and the last
+    // range may end with the vector; grid_ok (jh_lsqr_solve: one GPU, unpartitioned): an N x (2 .. 4) grid of equal elementwise blocks on its one-pass
+    // step (jh_grid_step.hip)
+    JH_TRY(sh.init(res, maxiter, [&](int k) { return ch || sh.tall(k) || (grid_ok && jhb::grid_step_ok(ops[k], us[k]->data, xs[k]->data, xs[k]->data)); },
+                   "a tall operator of >= 2 equal elementwise rows"));
+    std::vector<Passes> pass = passes_of(sh, ch);
+    std::vector<DomVecs<3>> t((size_t)M);
+    const int dtype = sh.dtype, grid = dom_grid(sh.n, dtype);
+    for (int k = 0; k < M; k++) {
+        JH_TRY(sh.use(k));
+        JH_TRY(t[k].create(sh.n, dtype, 2 * (size_t)grid + 2));           // 2 x grid per-workgroup partials + 2 result slots
+    }
+    auto parts_v = [&](int k) { return t[k].parts; };
+    auto parts_w = [&](int k) { return t[k].parts + grid; };
+    double *slot_v = t[0].parts + 2 * grid, *slot_w = slot_v + 1;        // member 0 folds and reports the domain-side norms
+    JH_TRY(sh.use(0));
+    jh_context &c = jh_ctx();                                            // member 0's context: its stream carries the read-backs
+    *res = jh_lsqr_result{};
+    LsqrDev h;
+    JH_TRY(lsqr_start(sh, pass, t, use_x0, damp, atol, btol, conlim, maxiter, force_maxiter, &h));
+    if (h.arnorm != 0) {
+        while (h.itn < maxiter) {
             // ---- bidiagonalisation in one pass:  beta*u = A v - alpha*u ;  alpha*v = A'u - beta*v
-            const double beta_prev = beta;
-            if (ex != Exch::none) {
-                // every shard's rows in 4 element ranges: the all-reduce of a finished range of A'u runs on the exchange stream while
-                // the kernel of the next range computes; ||u||^2 accumulates on the device and is summed behind the last range --
-                // ONE host synchronisation per shard for the whole distributed step
-                for (int k = 0; k < M; k++) { JH_TRY(use(k)); JH_TRY(jh_normsq_reset()); }
-                for (int64_t lo = 0; lo < n; lo += chunk) {
-                    const int64_t cnt = lo + chunk < n ? chunk : n - lo;
-                    for (int k = 0; k < M; k++)
-                        JH_TRY(jh_blockop_bidiag_step_range(ops[k], us[k], t[k].v, t[k].atu, 1.0, -alpha / beta_prev, lo, cnt, nullptr));
-                    JH_TRY(exchange([&](int k) { return jh_comm_allreduce_sum_range(t[k].atu, lo, cnt); }));
-                }
-                if (ex == Exch::ranks) {
-                    JH_TRY(jh_comm_allreduce_normsq(&s2));
-                } else {                                                 // team: the host adds the members' accumulators
-                    s2 = 0.0;
-                    for (int k = M - 1; k >= 0; k--) {                   // member 0 last: its synchronisation also lands wnorm (below)
-                        JH_TRY(use(k));
-                        JH_TRY(jh_comm_join());
-                        double part = 0.0;
-                        JH_TRY(jh_normsq_read(&part));
-                        s2 += part;
-                    }
-                }
-            } else {
-                JH_TRY(pass[0].step(us[0], t[0].v, t[0].atu, 1.0, -alpha / beta_prev, &s2));
-            }
-            beta = std::sqrt(s2);
-            if (wnorm_pending) {                                         // the step's read-back synchronised member 0's stream: it has landed
-                wnorm = std::sqrt(c.red_host[5]);
-                wnorm_pending = false;
-            }
-            double cv = 1.0;                                             // normalisation of v, applied by the x/w kernel below
-            if (beta > 0) {
-                anorm = std::sqrt(anorm * anorm + alpha * alpha + beta * beta + damp * damp);
+            double s2 = 0.0;
+            if (ex != Exch::none) JH_TRY(sh.ranged_step([&](int k) { return t[k][V]; }, [&](int k) { return t[k][ATU]; }, h.coef_step[0], h.coef_step[1], &s2));
+            else JH_TRY(pass[0].step(us[0], t[0][V], t[0][ATU], h.coef_step[0], h.coef_step[1], &s2));
+            // the step's read-back synchronised member 0's stream: ||w||^2 of the previous iteration (copied below) has landed in red_host[5]
+            lsqr_s1(&h, s2, c.red_host + 5);
+            if (!h.skipv) {
                 for (int k = M - 1; k >= 0; k--) {                       // v <- A'(u_hat)/beta - beta v, ||v||^2 (member 0 last: it reports)
-                    JH_TRY(use(k));
-                    JH_TRY(launch_vhat(dtype, t[k].v, t[k].atu, 1.0 / beta, -beta, parts_v(k), grid));
+                    JH_TRY(sh.use(k));
+                    JH_TRY(launch_vhat(dtype, t[k][V], t[k][ATU], h.coef_vhat[0], h.coef_vhat[1], parts_v(k), grid));
                 }
                 hipLaunchKernelGGL(k_lsqr_fold, dim3(1), dim3(256), 0, c.stream, parts_v(0), grid, slot_v);
                 JH_CHECK_HIP(hipGetLastError());
                 JH_CHECK_HIP(hipMemcpyAsync(c.red_host + 4, slot_v, sizeof(double), hipMemcpyDeviceToHost, c.stream));
                 JH_CHECK_HIP(hipStreamSynchronize(c.stream));
-                alpha = std::sqrt(c.red_host[4]);
-                if (alpha > 0) cv = 1.0 / alpha;
             }
-            // ---- eliminate the damping parameter, then the plane rotation
-            const double rhobar1 = std::sqrt(rhobar * rhobar + damp * damp);
-            const double rho = std::sqrt(rhobar1 * rhobar1 + beta * beta);
-            if (!(rhobar1 > 0 && std::isfinite(rho))) {                  // only reachable with force_maxiter, far past convergence: the recurrences
-                if (!istop) istop = 6;                                   // have underflowed; x is left at its last finite update
-                itn--;
-                break;
-            }
-            const double cs1 = rhobar / rhobar1, sn1 = damp / rhobar1;
-            const double psi = sn1 * phibar;
-            phibar = cs1 * phibar;
-            const double cs = rhobar1 / rho, sn = beta / rho;
-            const double theta = sn * alpha;
-            rhobar = -cs * alpha;
-            const double phi = cs * phibar;
-            phibar = sn * phibar;
-            const double tau = sn * phi;
-            // ---- update x and w
-            const double t1 = phi / rho, t2 = -theta / rho;
-            ddnorm += (wnorm / rho) * (wnorm / rho);
+            lsqr_s2(&h, c.red_host[4], history);
+            if (h.done) break;                                           // underflow far past convergence: x is left at its last finite update
             for (int k = M - 1; k >= 0; k--) {                           // v normalised; x += t1 w; w = v + t2 w; ||w||^2
-                JH_TRY(use(k));
-                JH_TRY(launch_xw(dtype, t[k].v, xs[k], t[k].w, cv, t1, t2, parts_w(k), grid));
+                JH_TRY(sh.use(k));
+                JH_TRY(launch_xw(dtype, t[k][V], xs[k], t[k][W], h.coef_xw[0], h.coef_xw[1], h.coef_xw[2], parts_w(k), grid));
             }
             hipLaunchKernelGGL(k_lsqr_fold, dim3(1), dim3(256), 0, c.stream, parts_w(0), grid, slot_w);
             JH_CHECK_HIP(hipGetLastError());
             JH_CHECK_HIP(hipMemcpyAsync(c.red_host + 5, slot_w, sizeof(double), hipMemcpyDeviceToHost, c.stream));   // read after the next sync
-            wnorm_pending = true;
-            // ---- norms for the stopping rules
-            const double delta = sn2 * rho, gambar = -cs2 * rho, rhs = phi - delta * z, zbar = rhs / gambar;
-            xnorm = std::sqrt(xxnorm + zbar * zbar);
-            const double gamma = std::sqrt(gambar * gambar + theta * theta);
-            cs2 = gambar / gamma;
-            sn2 = theta / gamma;
-            z = rhs / gamma;
-            xxnorm += z * z;
-            acond = anorm * std::sqrt(ddnorm);
-            const double res1 = phibar * phibar;
-            res2 += psi * psi;
-            rnorm = std::sqrt(res1 + res2);
-            arnorm = alpha * std::fabs(tau);
-            const double r1sq = rnorm * rnorm - damp * damp * xxnorm;
-            r1norm = std::sqrt(std::fabs(r1sq)) * (r1sq >= 0 ? 1.0 : -1.0);
-            r2norm = rnorm;
-            if (history) { history[2 * (itn - 1)] = r1norm; history[2 * (itn - 1) + 1] = arnorm; }
-            const double test1 = bnorm > 0 ? rnorm / bnorm : 0.0;
-            const double test2 = rnorm > 0 ? arnorm / (anorm * rnorm + eps) : 0.0;
-            const double test3 = 1.0 / (acond + eps);
-            const double t1_ = bnorm > 0 ? test1 / (1 + anorm * xnorm / bnorm) : 0.0;
-            const double rtol = bnorm > 0 ? btol + atol * anorm * xnorm / bnorm : 0.0;
-            if (itn >= maxiter) istop = 7;
-            if (1 + test3 <= 1) istop = 6;
-            if (1 + test2 <= 1) istop = 5;
-            if (1 + t1_ <= 1) istop = 4;
-            if (test3 <= ctol) istop = 3;
-            if (test2 <= atol) istop = 2;
-            if (test1 <= rtol) istop = 1;
-            if (istop && !(force_maxiter && itn < maxiter && alpha > 0 && beta > 0)) break;
+            if (h.pending) break;
         }
     }
-    res->istop = istop;
-    res->itn = itn;
-    res->r1norm = r1norm;
-    res->r2norm = r2norm;
-    res->anorm = anorm;
-    res->acond = acond;
-    res->arnorm = arnorm;
-    res->xnorm = xnorm;
-    for (int k = 0; k < M; k++) {                                        // the temporaries die here
-        jh_context *ck = jh_ctx_by_id(ops[k]->ctx);
-        if (ck) { JH_TRY(use(k)); JH_CHECK_HIP(hipStreamSynchronize(ck->stream)); }
-    }
-    return JH_OK;
+    lsqr_result_from(h, res);
+    return sh.sync_all();                                                // the temporaries die here
 }
 
 // The graph-replayed loop for ONE small operator in one context (see LsqrDev above).  *took = false: not eligible, nothing was
@@ -621,45 +686,19 @@ static int lsqr_graph_impl(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int use
     if (hipStreamIsCapturing(c.stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return JH_OK;
     *took = true;
 
-    Tmp t;
-    const int64_t len1[1] = {n};
-    JH_TRY(jh_bvec_create(1, len1, dtype, &t.v));
-    JH_TRY(jh_bvec_create(1, len1, dtype, &t.w));
-    JH_TRY(jh_bvec_create(1, len1, dtype, &t.atu));
-    const int64_t ns_dom = n * (jh_dtype_complex(dtype) ? 2 : 1);
-    int grid = (int)((ns_dom + 255) / 256 < 4096 ? (ns_dom + 255) / 256 : 4096);
-    if (grid < 1) grid = 1;
-    JH_CHECK_HIP(jh_device_malloc(jh_ctx().device, (void **)&t.parts, sizeof(double) * (2 * (size_t)grid + 2)));
+    Shards sh("jh_lsqr_solve", 1, &op, &u, &x, Exch::none);
+    JH_TRY(sh.init(res, maxiter, [](int) { return true; }, ""));
+    std::vector<Passes> pass = passes_of(sh, nullptr);
+    std::vector<DomVecs<3>> tv(1);
+    const int grid = dom_grid(n, dtype);
+    JH_TRY(tv[0].create(n, dtype, 2 * (size_t)grid + 2));
+    const DomVecs<3> &t = tv[0];
     double *parts_v = t.parts, *parts_w = t.parts + grid, *slot_v = t.parts + 2 * grid, *slot_w = slot_v + 1;
     *res = jh_lsqr_result{};
-
-    // ---- the start-up of lsqr_impl, one shard, no exchange
-    if (!use_x0) JH_TRY(jh_fill(x, 0.0, 0.0));
-    double nrm = 0.0;
-    JH_TRY(jh_norm(u, 2.0, &nrm));
-    const double bnorm = std::sqrt(nrm * nrm);
-    double beta = bnorm;
-    if (use_x0) {
-        double local = 0.0;
-        JH_TRY(jh_blockop_mul_axpby(op, u, x, -1.0, 1.0, &local));
-        beta = std::sqrt(local);
-    }
-    double alpha = 0.0;
-    if (beta > 0) {
-        JH_TRY(jh_blockop_mul_adj(op, t.atu, u));
-        JH_TRY(lincomb1(t.v, 1.0 / beta, t.atu));
-        JH_TRY(jh_norm(t.v, 2.0, &alpha));
-    } else {
-        JH_TRY(jh_copy(t.v, x));
-    }
-    if (alpha > 0) JH_TRY(lincomb1(t.v, 1.0 / alpha, t.v));
-    JH_TRY(jh_copy(t.w, t.v));
-    double wnorm = 0.0;
-    JH_TRY(jh_norm(t.w, 2.0, &wnorm));
-    const double arnorm0 = alpha * beta;
-    res->r1norm = res->r2norm = beta;
-    res->arnorm = arnorm0;
-    if (arnorm0 == 0) return JH_OK;                                       // (istop = itn = 0, like lsqr_impl)
+    LsqrDev h;
+    JH_TRY(lsqr_start(sh, pass, tv, use_x0, damp, atol, btol, conlim, maxiter, force_maxiter, &h));   // one shard, no exchange
+    lsqr_result_from(h, res);
+    if (h.arnorm == 0) return JH_OK;                                      // (istop = itn = 0, like lsqr_impl)
 
     // ---- device state
     struct Dev {
@@ -677,44 +716,23 @@ static int lsqr_graph_impl(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int use
     } d;
     JH_CHECK_HIP(jh_device_malloc(c.device, (void **)&d.st, sizeof(LsqrDev)));
     JH_CHECK_HIP(jh_device_malloc(c.device, (void **)&d.hist, sizeof(double) * 2 * (size_t)maxiter));
-    LsqrDev h{};
-    h.alpha = alpha;
-    h.beta = beta;
-    h.rhobar = alpha;
-    h.phibar = beta;
-    h.cs2 = -1.0;
-    h.bnorm = bnorm;
-    h.wnorm = wnorm;
-    h.damp = damp;
-    h.atol = atol;
-    h.btol = btol;
-    h.ctol = conlim > 0 ? 1.0 / conlim : 0.0;
-    h.r1norm = h.r2norm = beta;
-    h.arnorm = arnorm0;
-    h.coef_step[0] = 1.0;
-    h.coef_step[1] = -alpha / beta;
-    h.maxiter = maxiter;
-    h.force = force_maxiter ? 1 : 0;
     JH_CHECK_HIP(hipMemcpyAsync(d.st, &h, sizeof(h), hipMemcpyHostToDevice, c.stream));
     JH_CHECK_HIP(hipStreamSynchronize(c.stream));                        // `h` is a stack object
 
-    const bool f64 = (dtype == JH_F64 || dtype == JH_C64);
     // one iteration, enqueued on the context's stream: eagerly the first time (workspaces get their size), captured the second
     auto iteration = [&]() -> int {
         JH_TRY(jh_normsq_reset());
         c.step_coef_dev = d.st->coef_step;
         c.step_done_dev = &d.st->done;
-        const int st_ = jh_blockop_bidiag_step_range(op, u, t.v, t.atu, 1.0, 0.0, 0, n, nullptr);     // (alpha, beta) come from the device
+        const int st_ = jh_blockop_bidiag_step_range(op, u, t[V], t[ATU], 1.0, 0.0, 0, n, nullptr);     // (alpha, beta) come from the device
         c.step_coef_dev = nullptr;
         c.step_done_dev = nullptr;
         JH_TRY(st_);
         hipLaunchKernelGGL(k_lsqr_s1, dim3(1), dim3(1), 0, c.stream, d.st, (const double *)(c.red_dev + JH_NORMSQ_SLOT), (const double *)slot_w);
-        if (f64) hipLaunchKernelGGL((k_lsqr_vhat_dev<double>), dim3(grid), dim3(256), 0, c.stream, (double *)t.v->data, (const double *)t.atu->data, ns_dom, (const LsqrDev *)d.st, parts_v);
-        else hipLaunchKernelGGL((k_lsqr_vhat_dev<float>), dim3(grid), dim3(256), 0, c.stream, (float *)t.v->data, (const float *)t.atu->data, ns_dom, (const LsqrDev *)d.st, parts_v);
+        JH_TRY(launch_vhat_dev(dtype, t[V], t[ATU], d.st, parts_v, grid));
         hipLaunchKernelGGL(k_lsqr_fold, dim3(1), dim3(256), 0, c.stream, (const double *)parts_v, grid, slot_v);
         hipLaunchKernelGGL(k_lsqr_s2, dim3(1), dim3(1), 0, c.stream, d.st, (const double *)slot_v, d.hist);
-        if (f64) hipLaunchKernelGGL((k_lsqr_xw_dev<double>), dim3(grid), dim3(256), 0, c.stream, (double *)t.v->data, (double *)x->data, (double *)t.w->data, ns_dom, (const LsqrDev *)d.st, parts_w);
-        else hipLaunchKernelGGL((k_lsqr_xw_dev<float>), dim3(grid), dim3(256), 0, c.stream, (float *)t.v->data, (float *)x->data, (float *)t.w->data, ns_dom, (const LsqrDev *)d.st, parts_w);
+        JH_TRY(launch_xw_dev(dtype, t[V], x, t[W], d.st, parts_w, grid));
         hipLaunchKernelGGL(k_lsqr_fold, dim3(1), dim3(256), 0, c.stream, (const double *)parts_w, grid, slot_w);
         hipLaunchKernelGGL(k_lsqr_s3, dim3(1), dim3(1), 0, c.stream, d.st);
         JH_CHECK_HIP(hipGetLastError());
@@ -726,17 +744,15 @@ static int lsqr_graph_impl(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int use
         c.step_coef_dev = d.st->coef_step;
         c.step_done_dev = &d.st->halt;
         c.step_skip_fold = 1;
-        const int st_ = jh_blockop_bidiag_step_range(op, u, t.v, t.atu, 1.0, 0.0, 0, n, nullptr);
+        const int st_ = jh_blockop_bidiag_step_range(op, u, t[V], t[ATU], 1.0, 0.0, 0, n, nullptr);
         c.step_coef_dev = nullptr;
         c.step_done_dev = nullptr;
         c.step_skip_fold = 0;
         JH_TRY(st_);
         hipLaunchKernelGGL(k_lsqr_fold_s1, dim3(1), dim3(256), 0, c.stream, (const double *)c.part_dev, c.last_step_parts, d.st, (const double *)parts_w, grid, slot_w);
-        if (f64) hipLaunchKernelGGL((k_lsqr_vhat_dev<double>), dim3(grid), dim3(256), 0, c.stream, (double *)t.v->data, (const double *)t.atu->data, ns_dom, (const LsqrDev *)d.st, parts_v);
-        else hipLaunchKernelGGL((k_lsqr_vhat_dev<float>), dim3(grid), dim3(256), 0, c.stream, (float *)t.v->data, (const float *)t.atu->data, ns_dom, (const LsqrDev *)d.st, parts_v);
+        JH_TRY(launch_vhat_dev(dtype, t[V], t[ATU], d.st, parts_v, grid));
         hipLaunchKernelGGL(k_lsqr_fold_s2, dim3(1), dim3(256), 0, c.stream, (const double *)parts_v, grid, d.st, d.hist);
-        if (f64) hipLaunchKernelGGL((k_lsqr_xw_dev<double>), dim3(grid), dim3(256), 0, c.stream, (double *)t.v->data, (double *)x->data, (double *)t.w->data, ns_dom, (const LsqrDev *)d.st, parts_w);
-        else hipLaunchKernelGGL((k_lsqr_xw_dev<float>), dim3(grid), dim3(256), 0, c.stream, (float *)t.v->data, (float *)x->data, (float *)t.w->data, ns_dom, (const LsqrDev *)d.st, parts_w);
+        JH_TRY(launch_xw_dev(dtype, t[V], x, t[W], d.st, parts_w, grid));
         JH_CHECK_HIP(hipGetLastError());
         return JH_OK;
     };
@@ -773,14 +789,40 @@ static int lsqr_graph_impl(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int use
         JH_CHECK_HIP(hipMemcpyAsync(history, d.hist, sizeof(double) * 2 * (size_t)h.itn, hipMemcpyDeviceToHost, c.stream));
         JH_CHECK_HIP(hipStreamSynchronize(c.stream));
     }
-    res->istop = h.istop;
-    res->itn = h.itn;
-    res->r1norm = h.r1norm;
-    res->r2norm = h.r2norm;
-    res->anorm = h.anorm;
-    res->acond = h.acond;
-    res->arnorm = h.arnorm;
-    res->xnorm = h.xnorm;
+    lsqr_result_from(h, res);
+    return JH_OK;
+}
+
+// ---- what the entry points of the three solvers check alike; `who` is the solver's plain entry, whose name the messages extend ----
+// jh_*_solve_partitioned: the communicator is the one of the handles' context.  One rank: nothing to exchange (jh_comm_init_rank is then optional, so a
+// one-GPU run of partitioned host code works); the knob force_dist runs the exchange all the same (validation of the pipelined path with a one-rank
+// communicator)
+static int partitioned_exchange(const char *who, const jh_blockop *op, const jh_bvec *u, const jh_bvec *x, Exch *ex)
+{
+    JH_TRY(jh_enter(op, u, x));
+    int nranks = 1, rank = 0, has_comm = 0;
+    (void)jh_comm_info(&nranks, &rank);
+    (void)jh_comm_exists(&has_comm);
+    if (has_comm == 2 && (nranks > 1 || jh_ctx().force_dist))
+        return jh_fail(JH_ERR_UNSUPPORTED, "%s_partitioned: this context is a member of a single-process team (jh_comm_init_all): "
+                       "%s_team takes all the members' shards in one call", who, who);
+    *ex = (nranks > 1 || (has_comm && jh_ctx().force_dist)) ? Exch::ranks : Exch::none;
+    return JH_OK;
+}
+
+// jh_*_solve_team: member k's handles live in member k's context of a team of n
+static int team_members_ok(const char *who, int n, const jh_blockop *const *ops, jh_bvec *const *us, jh_bvec *const *xs)
+{
+    JH_REQUIRE(n >= 1 && n <= JH_MAX_CTX && ops && us && xs, "%s_team: need 1..%d members", who, JH_MAX_CTX);
+    for (int k = 0; k < n; k++) {
+        JH_REQUIRE(ops[k] && us[k] && xs[k], "%s_team: null handle of member %d", who, k);
+        JH_TRY(jh_enter(ops[k], us[k], xs[k]));
+        int nranks = 1, rank = 0, has_comm = 0;
+        (void)jh_comm_info(&nranks, &rank);
+        (void)jh_comm_exists(&has_comm);
+        JH_REQUIRE(has_comm == 2 && nranks == n && rank == k, "%s_team: the handles of member %d must live in member %d's context of a team of %d "
+                   "(jh_comm_init_all); found %s, rank %d of %d", who, k, k, n, has_comm == 2 ? "a team" : "no team", rank, nranks);
+    }
     return JH_OK;
 }
 
@@ -796,17 +838,9 @@ extern "C" int jh_lsqr_solve(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int u
 extern "C" int jh_lsqr_solve_partitioned(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int use_x0, double damp, double atol, double btol,
                                          double conlim, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history)
 {
-    JH_TRY(jh_enter(op, u, x));                                         // the communicator is the one of the handles' context
-    int nranks = 1, rank = 0, has_comm = 0;
-    (void)jh_comm_info(&nranks, &rank);
-    (void)jh_comm_exists(&has_comm);
-    if (has_comm == 2 && (nranks > 1 || jh_ctx().force_dist))
-        return jh_fail(JH_ERR_UNSUPPORTED, "jh_lsqr_solve_partitioned: this context is a member of a single-process team (jh_comm_init_all): "
-                       "jh_lsqr_solve_team takes all the members' shards in one call");
-    // one rank: nothing to exchange (jh_comm_init_rank is then optional, so a one-GPU run of partitioned host code works);
-    // the knob force_dist runs the exchange all the same (validation of the pipelined path with a one-rank communicator)
-    return lsqr_impl(1, &op, &u, &x, use_x0, damp, atol, btol, conlim, maxiter, force_maxiter, res, history,
-                     (nranks > 1 || (has_comm && jh_ctx().force_dist)) ? Exch::ranks : Exch::none);
+    Exch ex = Exch::none;
+    JH_TRY(partitioned_exchange("jh_lsqr_solve", op, u, x, &ex));
+    return lsqr_impl(1, &op, &u, &x, use_x0, damp, atol, btol, conlim, maxiter, force_maxiter, res, history, ex);
 }
 
 // ONE process, a team of n member contexts (jh_comm_init_all): member k holds ops[k] (its block rows), us[k] (its rows of the
@@ -815,16 +849,7 @@ extern "C" int jh_lsqr_solve_partitioned(const jh_blockop *op, jh_bvec *u, jh_bv
 extern "C" int jh_lsqr_solve_team(int n, const jh_blockop *const *ops, jh_bvec *const *us, jh_bvec *const *xs, int use_x0, double damp, double atol,
                                   double btol, double conlim, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history)
 {
-    JH_REQUIRE(n >= 1 && n <= JH_MAX_CTX && ops && us && xs, "jh_lsqr_solve_team: need 1..%d members", JH_MAX_CTX);
-    for (int k = 0; k < n; k++) {
-        JH_REQUIRE(ops[k] && us[k] && xs[k], "jh_lsqr_solve_team: null handle of member %d", k);
-        JH_TRY(jh_enter(ops[k], us[k], xs[k]));
-        int nranks = 1, rank = 0, has_comm = 0;
-        (void)jh_comm_info(&nranks, &rank);
-        (void)jh_comm_exists(&has_comm);
-        JH_REQUIRE(has_comm == 2 && nranks == n && rank == k, "jh_lsqr_solve_team: the handles of member %d must live in member %d's context of a team of %d "
-                   "(jh_comm_init_all); found %s, rank %d of %d", k, k, n, has_comm == 2 ? "a team" : "no team", rank, nranks);
-    }
+    JH_TRY(team_members_ok("jh_lsqr_solve", n, ops, us, xs));
     return lsqr_impl(n, ops, us, xs, use_x0, damp, atol, btol, conlim, maxiter, force_maxiter, res, history, Exch::team);
 }
 
@@ -849,98 +874,42 @@ static int cgls_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
                      double btol, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history, const Exch ex,
                      const jh_chain *ch = nullptr, const bool grid_ok = false)
 {
-    JH_REQUIRE(ops && us && xs && res && M >= 1, "jh_cgls_solve: null argument");
-    JH_REQUIRE(maxiter >= 0, "jh_cgls_solve: maxiter must be >= 0");
-    for (int k = 0; k < M; k++) JH_REQUIRE(ops[k] && us[k] && xs[k], "jh_cgls_solve: null argument (member %d)", k);
-    auto use = [&](int k) { return jh_enter(ops[k], us[k], xs[k]); };
-    JH_TRY(use(0));
-    int64_t nb = 0, n = 0;
-    int dtype = 0;
-    JH_TRY(jh_bvec_info(xs[0], &nb, &n, &dtype, nullptr));
+    Shards sh("jh_cgls_solve", M, ops, us, xs, ex);
+    // a chain; a tall operator (rows off the 16-byte pack grid too, as in lsqr_impl) of two rows or more; grid_ok (jh_cgls_solve: one GPU, unpartitioned): an
+    // N x (2 .. 4) grid of equal elementwise blocks -- its one-pass step (jh_grid_step.hip) and its fused A'A (jh_grid_normal.hip) are both asked
+    JH_TRY(sh.init(res, maxiter, [&](int k) {
+        if (ch) return true;
+        if (sh.tall(k)) return ops[k]->nrow >= 2;
+        return grid_ok && jhb::grid_step_ok(ops[k], us[k]->data, xs[k]->data, xs[k]->data) && jhb::grid_normal_ok(ops[k], xs[k]->data, xs[k]->data);
+    }, "a tall (>= 2 rows) operator of equal elementwise rows"));
+    std::vector<Passes> pass = passes_of(sh, ch);
+    std::vector<DomVecs<3>> t((size_t)M);
     for (int k = 0; k < M; k++) {
-        JH_REQUIRE(xs[k]->length == n && xs[k]->dtype == dtype, "jh_cgls_solve: member %d's x differs in length or element type", k);
-        // before anything is touched (rows off the 16-byte pack grid too, as in lsqr_impl)
-        // grid_ok (jh_cgls_solve: one GPU, unpartitioned): an N x (2 .. 4) grid of equal elementwise blocks -- its one-pass step (jh_grid_step.hip) and its
-        // fused A'A (jh_grid_normal.hip) are both checked here
-        const bool grid = grid_ok && !ch && M == 1 && ex == Exch::none && !jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data) &&
-                          jhb::grid_step_ok(ops[k], us[k]->data, xs[k]->data, xs[k]->data) && jhb::grid_normal_ok(ops[k], xs[k]->data, xs[k]->data);
-        if (!ch && !grid && (!jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data) || ops[k]->nrow < 2))
-            return jh_fail(JH_ERR_UNSUPPORTED, "jh_cgls_solve: needs a tall (>= 2 rows) operator of equal elementwise rows");
-    }
-    std::vector<Passes> pass((size_t)M);
-    for (int k = 0; k < M; k++) { pass[k].op = ops[k]; pass[k].ch = ch; pass[k].grid = !ch && !jh_blockop_tall_step_ok(ops[k], us[k]->data, xs[k]->data); }
-    struct Work {                                                         // domain-sized work vectors of one member
-        jh_bvec *p = nullptr, *s = nullptr, *y = nullptr;
-        ~Work()
-        {
-            if (p) (void)jh_bvec_destroy(p);
-            if (s) (void)jh_bvec_destroy(s);
-            if (y) (void)jh_bvec_destroy(y);
-        }
-    };
-    std::vector<Work> t((size_t)M);
-    const int64_t len1[1] = {n};
-    for (int k = 0; k < M; k++) {
-        JH_TRY(use(k));
-        JH_TRY(jh_bvec_create(1, len1, dtype, &t[k].p));
-        JH_TRY(jh_bvec_create(1, len1, dtype, &t[k].s));
-        JH_TRY(jh_bvec_create(1, len1, dtype, &t[k].y));
+        JH_TRY(sh.use(k));
+        JH_TRY(t[k].create(sh.n, sh.dtype));
     }
     *res = jh_lsqr_result{};
-    int64_t chunk = (n + 3) / 4;                                          // exchange ranges: 4, on 64 KiB boundaries (as lsqr_impl)
-    chunk = (chunk + 16383) / 16384 * 16384;
-    auto global_sum = [&](const std::vector<double> &locals, double *out) -> int {
-        double sum = 0.0;
-        for (double v : locals) sum += v;
-        *out = sum;
-        if (ex == Exch::ranks) JH_TRY(jh_comm_allreduce_scalars(out, 1, 0));
-        return JH_OK;
-    };
-    auto exchange = [&](auto &&one) -> int {
-        if (ex == Exch::none) return JH_OK;
-        if (ex == Exch::team) { JH_TRY(use(0)); JH_TRY(jh_comm_group_begin()); }
-        int st = JH_OK;
-        for (int k = 0; k < M && st == JH_OK; k++) st = one(k);
-        if (ex == Exch::team) { (void)use(0); const int st2 = jh_comm_group_end(); if (st == JH_OK) st = st2; }
-        return st;
-    };
-    auto lincomb2 = [&](jh_bvec *dst, double c0, const jh_bvec *x0, double c1, const jh_bvec *x1) {
-        const double coef[4] = {c0, 0.0, c1, 0.0};
-        const jh_bvec *v[2] = {x0, x1};
-        return jh_lincomb(dst, 2, coef, v);
-    };
-    // s = A'r (already summed over the shards, in t[k].s) - damp^2 x ;  returns ||s||^2 (member 0 speaks for all: replicas are identical)
+    // s = A'r (already summed over the shards, in t[k][S]) - damp^2 x ;  returns ||s||^2 (member 0 speaks for all: replicas are identical)
     auto finish_s = [&](double *gamma) -> int {
         for (int k = 0; k < M; k++)
-            if (damp != 0.0) JH_TRY(lincomb2(t[k].s, 1.0, t[k].s, -damp * damp, xs[k]));
+            if (damp != 0.0) JH_TRY(lincomb2(t[k][S], 1.0, t[k][S], -damp * damp, xs[k]));
         double nrm = 0.0;
-        JH_TRY(jh_norm(t[0].s, 2.0, &nrm));
+        JH_TRY(jh_norm(t[0][S], 2.0, &nrm));
         *gamma = nrm * nrm;
         return JH_OK;
     };
-    std::vector<double> locals((size_t)M);
+    std::vector<double> &locals = sh.locals;
     jh_context *const trace_ctx = jh_ctx_by_id(ops[0]->ctx);              // knob cgls_trace / read-only last_cgls_overlaps live in member 0's context
     if (trace_ctx) trace_ctx->last_cgls_overlaps = -1;
 
-    double s2 = 0.0;
-    for (int k = 0; k < M; k++) {
-        if (!use_x0) JH_TRY(jh_fill(xs[k], 0.0, 0.0));
-        double nrm = 0.0;
-        JH_TRY(jh_norm(us[k], 2.0, &nrm));                               // ||b|| (this shard's rows)
-        locals[k] = nrm * nrm;
-    }
-    JH_TRY(global_sum(locals, &s2));
+    double s2 = 0.0, rr = 0.0;                                            // ||b||^2 ;  ||r||^2, r <- b - A x0 in the right-hand side's storage
+    JH_TRY(start_residual(sh, pass, use_x0, &s2, &rr));
     const double bnorm = std::sqrt(s2);
-    double rr = s2;                                                       // ||r||^2
-    if (use_x0) {                                                         // r <- b - A x0
-        for (int k = 0; k < M; k++) JH_TRY(pass[k].fwd_axpby(us[k], xs[k], -1.0, 1.0, &locals[k]));
-        JH_TRY(global_sum(locals, &rr));
-    }
-    for (int k = 0; k < M; k++) JH_TRY(pass[k].adjoint(t[k].s, us[k]));                     // s = A'r
-    JH_TRY(exchange([&](int k) { return jh_comm_allreduce_sum(t[k].s); }));
+    for (int k = 0; k < M; k++) JH_TRY(pass[k].adjoint(t[k][S], us[k]));                     // s = A'r
+    JH_TRY(sh.grouped([&](int k) { return jh_comm_allreduce_sum(t[k][S]); }));
     double gamma = 0.0;
     JH_TRY(finish_s(&gamma));
-    for (int k = 0; k < M; k++) JH_TRY(jh_copy(t[k].p, t[k].s));
+    for (int k = 0; k < M; k++) JH_TRY(jh_copy(t[k][P], t[k][S]));
     const double gamma0 = gamma;
     double xnorm = 0.0;
     int itn = 0, istop = 0;
@@ -954,20 +923,20 @@ static int cgls_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
             std::vector<hipEvent_t> tev(trace ? (size_t)(2 * M) : 0, nullptr);
             auto stamp = [&](int k, int which) -> int {
                 if (!trace) return JH_OK;
-                JH_TRY(use(k));
+                JH_TRY(sh.use(k));
                 JH_CHECK_HIP(hipEventCreate(&tev[(size_t)(2 * k + which)]));
                 JH_CHECK_HIP(hipEventRecord(tev[(size_t)(2 * k + which)], jh_ctx().stream));
                 return JH_OK;
             };
             for (int k = 0; k < M; k++) {
                 JH_TRY(stamp(k, 0));
-                JH_TRY(pass[k].normal(t[k].y, t[k].p));
-                JH_TRY(jh_dot_begin(t[k].p, t[k].y));
+                JH_TRY(pass[k].normal(t[k][Y], t[k][P]));
+                JH_TRY(jh_dot_begin(t[k][P], t[k][Y]));
                 JH_TRY(stamp(k, 1));
             }
             for (int k = 0; k < M; k++) {
                 double re = 0.0, im = 0.0;
-                JH_TRY(jh_dot_end(t[k].p, &re, &im));
+                JH_TRY(jh_dot_end(t[k][P], &re, &im));
                 locals[k] = re;
             }
             if (trace) {                                                  // member k + 1 began before member k had finished?  (members of ONE device: one clock)
@@ -982,10 +951,10 @@ static int cgls_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
                     if (e) (void)hipEventDestroy(e);
             }
             double delta = 0.0;
-            JH_TRY(global_sum(locals, &delta));
+            JH_TRY(sh.sum(locals, &delta));
             if (damp != 0.0) {
                 double pn = 0.0;
-                JH_TRY(jh_norm(t[0].p, 2.0, &pn));
+                JH_TRY(jh_norm(t[0][P], 2.0, &pn));
                 delta += damp * damp * pn * pn;
             }
             if (!(delta > 0) || !std::isfinite(delta)) {                  // breakdown: p in the null space (or the recurrences have underflowed)
@@ -994,34 +963,14 @@ static int cgls_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
                 break;
             }
             const double alpha = gamma / delta;
-            for (int k = 0; k < M; k++) JH_TRY(lincomb2(xs[k], 1.0, xs[k], alpha, t[k].p));   // x += alpha p
+            for (int k = 0; k < M; k++) JH_TRY(lincomb2(xs[k], 1.0, xs[k], alpha, t[k][P]));   // x += alpha p
             // ---- pass 2: r <- r - alpha A p, ||r||^2 and A'r in ONE pass over the operator and r
-            if (ex != Exch::none) {
-                for (int k = 0; k < M; k++) { JH_TRY(use(k)); JH_TRY(jh_normsq_reset()); }
-                for (int64_t lo = 0; lo < n; lo += chunk) {
-                    const int64_t cnt = lo + chunk < n ? chunk : n - lo;
-                    for (int k = 0; k < M; k++) JH_TRY(jh_blockop_bidiag_step_range(ops[k], us[k], t[k].p, t[k].s, -alpha, 1.0, lo, cnt, nullptr));
-                    JH_TRY(exchange([&](int k) { return jh_comm_allreduce_sum_range(t[k].s, lo, cnt); }));
-                }
-                if (ex == Exch::ranks) {
-                    JH_TRY(jh_comm_allreduce_normsq(&rr));
-                } else {
-                    rr = 0.0;
-                    for (int k = M - 1; k >= 0; k--) {
-                        JH_TRY(use(k));
-                        JH_TRY(jh_comm_join());
-                        double part = 0.0;
-                        JH_TRY(jh_normsq_read(&part));
-                        rr += part;
-                    }
-                }
-            } else {
-                JH_TRY(pass[0].step(us[0], t[0].p, t[0].s, -alpha, 1.0, &rr));
-            }
+            if (ex != Exch::none) JH_TRY(sh.ranged_step([&](int k) { return t[k][P]; }, [&](int k) { return t[k][S]; }, -alpha, 1.0, &rr));
+            else JH_TRY(pass[0].step(us[0], t[0][P], t[0][S], -alpha, 1.0, &rr));
             double gamma_new = 0.0;
             JH_TRY(finish_s(&gamma_new));
             const double bk = gamma_new / gamma;
-            for (int k = 0; k < M; k++) JH_TRY(lincomb2(t[k].p, 1.0, t[k].s, bk, t[k].p));   // p = s + beta p
+            for (int k = 0; k < M; k++) JH_TRY(lincomb2(t[k][P], 1.0, t[k][S], bk, t[k][P]));   // p = s + beta p
             gamma = gamma_new;
             const double rnorm = std::sqrt(rr), arnorm = std::sqrt(gamma);
             if (history) { history[2 * (itn - 1)] = rnorm; history[2 * (itn - 1) + 1] = arnorm; }
@@ -1040,11 +989,7 @@ static int cgls_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
     res->acond = 0.0;
     res->arnorm = std::sqrt(gamma);
     res->xnorm = xnorm;
-    for (int k = 0; k < M; k++) {                                         // the temporaries die here
-        jh_context *ck = jh_ctx_by_id(ops[k]->ctx);
-        if (ck) { JH_TRY(use(k)); JH_CHECK_HIP(hipStreamSynchronize(ck->stream)); }
-    }
-    return JH_OK;
+    return sh.sync_all();                                                 // the temporaries die here
 }
 
 // ------------------------------------------------------------------ CGLS and CG on the normal equations for SMALL operators (round 4) -----
@@ -1194,19 +1139,13 @@ static int cg_dev_impl(const jh_blockop *op, jh_bvec *b, jh_bvec *x, int use_x0,
     JH_TRY(jh_bvec_create(1, len1, dtype, &t.y));
     const bool f64 = (dtype == JH_F64 || dtype == JH_C64);
     const int64_t ns_dom = n * (jh_dtype_complex(dtype) ? 2 : 1);
-    int grid = (int)((ns_dom + 255) / 256 < 4096 ? (ns_dom + 255) / 256 : 4096);
-    if (grid < 1) grid = 1;
+    const int grid = dom_grid(n, dtype);
     const int64_t packs = (n * (int64_t)jh_dtype_size(dtype)) / 16, grid_n = (packs + 255) / 256;
     JH_CHECK_HIP(jh_device_malloc(c.device, (void **)&t.parts, sizeof(double) * ((size_t)grid_n + (size_t)grid + 2)));
     JH_CHECK_HIP(jh_device_malloc(c.device, (void **)&t.hist, sizeof(double) * 2 * (size_t)maxiter));
     JH_CHECK_HIP(jh_device_malloc(c.device, (void **)&t.st, sizeof(jh_cg_dev)));
     double *parts_n = t.parts, *parts_s = t.parts + grid_n, *slots = parts_s + grid;
     *res = jh_lsqr_result{};
-    auto lincomb2 = [&](jh_bvec *dst, double c0, const jh_bvec *x0, double c1, const jh_bvec *x1) {
-        const double coef[4] = {c0, 0.0, c1, 0.0};
-        const jh_bvec *v[2] = {x0, x1};
-        return jh_lincomb(dst, 2, coef, v);
-    };
 
     // ---- the start-up of cgls_impl / cgnr_impl (one shard, no exchange)
     if (!use_x0) JH_TRY(jh_fill(x, 0.0, 0.0));
@@ -1390,30 +1329,15 @@ extern "C" int jh_cgls_solve(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int u
 extern "C" int jh_cgls_solve_partitioned(const jh_blockop *op, jh_bvec *u, jh_bvec *x, int use_x0, double damp, double atol, double btol,
                                          int maxiter, int force_maxiter, jh_lsqr_result *res, double *history)
 {
-    JH_TRY(jh_enter(op, u, x));
-    int nranks = 1, rank = 0, has_comm = 0;
-    (void)jh_comm_info(&nranks, &rank);
-    (void)jh_comm_exists(&has_comm);
-    if (has_comm == 2 && (nranks > 1 || jh_ctx().force_dist))
-        return jh_fail(JH_ERR_UNSUPPORTED, "jh_cgls_solve_partitioned: this context is a member of a single-process team (jh_comm_init_all): "
-                       "jh_cgls_solve_team takes all the members' shards in one call");
-    return cgls_impl(1, &op, &u, &x, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history,
-                     (nranks > 1 || (has_comm && jh_ctx().force_dist)) ? Exch::ranks : Exch::none);
+    Exch ex = Exch::none;
+    JH_TRY(partitioned_exchange("jh_cgls_solve", op, u, x, &ex));
+    return cgls_impl(1, &op, &u, &x, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history, ex);
 }
 
 extern "C" int jh_cgls_solve_team(int n, const jh_blockop *const *ops, jh_bvec *const *us, jh_bvec *const *xs, int use_x0, double damp, double atol,
                                   double btol, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history)
 {
-    JH_REQUIRE(n >= 1 && n <= JH_MAX_CTX && ops && us && xs, "jh_cgls_solve_team: need 1..%d members", JH_MAX_CTX);
-    for (int k = 0; k < n; k++) {
-        JH_REQUIRE(ops[k] && us[k] && xs[k], "jh_cgls_solve_team: null handle of member %d", k);
-        JH_TRY(jh_enter(ops[k], us[k], xs[k]));
-        int nranks = 1, rank = 0, has_comm = 0;
-        (void)jh_comm_info(&nranks, &rank);
-        (void)jh_comm_exists(&has_comm);
-        JH_REQUIRE(has_comm == 2 && nranks == n && rank == k, "jh_cgls_solve_team: the handles of member %d must live in member %d's context of a team of %d "
-                   "(jh_comm_init_all); found %s, rank %d of %d", k, k, n, has_comm == 2 ? "a team" : "no team", rank, nranks);
-    }
+    JH_TRY(team_members_ok("jh_cgls_solve", n, ops, us, xs));
     return cgls_impl(n, ops, us, xs, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history, Exch::team);
 }
 
@@ -1433,83 +1357,35 @@ static int cgnr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
                      double btol, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history, const Exch ex,
                      const jh_chain *ch = nullptr)
 {
-    JH_REQUIRE(ops && bs && xs && res && M >= 1, "jh_cgnr_solve: null argument");
-    JH_REQUIRE(maxiter >= 0, "jh_cgnr_solve: maxiter must be >= 0");
-    for (int k = 0; k < M; k++) JH_REQUIRE(ops[k] && bs[k] && xs[k], "jh_cgnr_solve: null argument (member %d)", k);
-    auto use = [&](int k) { return jh_enter(ops[k], bs[k], xs[k]); };
-    JH_TRY(use(0));
-    int64_t nb = 0, n = 0;
-    int dtype = 0;
-    JH_TRY(jh_bvec_info(xs[0], &nb, &n, &dtype, nullptr));
+    Shards sh("jh_cgnr_solve", M, ops, bs, xs, ex);
+    // a chain; a tall operator of two rows or more; (round 6) one unpartitioned shard may also be an N x (2 .. 4) grid of equal diagonals -- its fused A'A is
+    // jh_grid_normal.hip; the loop below only ever calls jh_blockop_mul_adj and jh_blockop_normal_mul on whole vectors there
+    JH_TRY(sh.init(res, maxiter, [&](int k) {
+        if (ch || (M == 1 && ex == Exch::none && jhb::grid_normal_ok(ops[k], xs[k]->data, xs[k]->data))) return true;
+        return sh.tall(k) && ops[k]->nrow >= 2;
+    }, "a tall (>= 2 rows) operator of equal elementwise rows (or, unpartitioned, an N x (2 .. 4) grid of equal diagonals)"));
+    std::vector<Passes> pass = passes_of(sh, ch);
+    std::vector<DomVecs<3>> t((size_t)M);
     for (int k = 0; k < M; k++) {
-        JH_REQUIRE(xs[k]->length == n && xs[k]->dtype == dtype, "jh_cgnr_solve: member %d's x differs in length or element type", k);
-        // (round 6: one shard may also be an N x (2 .. 4) grid of equal diagonals -- its fused A'A is jh_grid_normal.hip; the loop below only ever calls
-        // jh_blockop_mul_adj and jh_blockop_normal_mul on whole vectors there)
-        const bool grid = M == 1 && ex == Exch::none && jhb::grid_normal_ok(ops[k], xs[k]->data, xs[k]->data);
-        if (!ch && !grid && (!jh_blockop_tall_step_ok(ops[k], bs[k]->data, xs[k]->data) || ops[k]->nrow < 2))
-            return jh_fail(JH_ERR_UNSUPPORTED, "jh_cgnr_solve: needs a tall (>= 2 rows) operator of equal elementwise rows (or, unpartitioned, an N x (2 .. 4) grid of equal diagonals)");
-    }
-    struct Work {
-        jh_bvec *p = nullptr, *s = nullptr, *y = nullptr;
-        ~Work()
-        {
-            if (p) (void)jh_bvec_destroy(p);
-            if (s) (void)jh_bvec_destroy(s);
-            if (y) (void)jh_bvec_destroy(y);
-        }
-    };
-    std::vector<Passes> pass((size_t)M);
-    for (int k = 0; k < M; k++) { pass[k].op = ops[k]; pass[k].ch = ch; }
-    std::vector<Work> t((size_t)M);
-    const int64_t len1[1] = {n};
-    for (int k = 0; k < M; k++) {
-        JH_TRY(use(k));
-        JH_TRY(jh_bvec_create(1, len1, dtype, &t[k].p));
-        JH_TRY(jh_bvec_create(1, len1, dtype, &t[k].s));
-        JH_TRY(jh_bvec_create(1, len1, dtype, &t[k].y));
+        JH_TRY(sh.use(k));
+        JH_TRY(t[k].create(sh.n, sh.dtype));
     }
     *res = jh_lsqr_result{};
-    auto global_sum = [&](const std::vector<double> &locals, double *out) -> int {
-        double sum = 0.0;
-        for (double v : locals) sum += v;
-        *out = sum;
-        if (ex == Exch::ranks) JH_TRY(jh_comm_allreduce_scalars(out, 1, 0));
-        return JH_OK;
-    };
-    auto allreduce = [&](auto &&vec_of) -> int {                         // every member's domain vector summed over the shards
-        if (ex == Exch::none) return JH_OK;
-        if (ex == Exch::team) { JH_TRY(use(0)); JH_TRY(jh_comm_group_begin()); }
-        int st = JH_OK;
-        for (int k = 0; k < M && st == JH_OK; k++) st = jh_comm_allreduce_sum(vec_of(k));
-        if (ex == Exch::team) { (void)use(0); const int st2 = jh_comm_group_end(); if (st == JH_OK) st = st2; }
-        return st;
-    };
-    auto lincomb2 = [&](jh_bvec *dst, double c0, const jh_bvec *x0, double c1, const jh_bvec *x1) {
-        const double coef[4] = {c0, 0.0, c1, 0.0};
-        const jh_bvec *v[2] = {x0, x1};
-        return jh_lincomb(dst, 2, coef, v);
-    };
-    std::vector<double> locals((size_t)M);
+    auto allreduce = [&](int which) { return sh.grouped([&](int k) { return jh_comm_allreduce_sum(t[k][which]); }); };   // every member's domain vector summed over the shards
 
     // ||b||, s = A'b
     double s2 = 0.0;
-    for (int k = 0; k < M; k++) {
-        if (!use_x0) JH_TRY(jh_fill(xs[k], 0.0, 0.0));
-        double nrm = 0.0;
-        JH_TRY(jh_norm(bs[k], 2.0, &nrm));
-        locals[k] = nrm * nrm;
-    }
-    JH_TRY(global_sum(locals, &s2));
+    JH_TRY(start_norm_b(sh, use_x0, &s2));
     const double bnorm = std::sqrt(s2);
-    for (int k = 0; k < M; k++) JH_TRY(pass[k].adjoint(t[k].s, bs[k]));
-    JH_TRY(allreduce([&](int k) { return t[k].s; }));
+    for (int k = 0; k < M; k++) JH_TRY(pass[k].adjoint(t[k][S], bs[k]));
+    JH_TRY(allreduce(S));
     double rr = s2;                                                       // ||b - A x||^2, by recurrence
     if (use_x0) {                                                         // s = A'b - (A'A + damp^2) x0 ;  ||r0||^2 = ||b||^2 - 2 Re<x0, A'b> + <x0, A'A x0>
-        for (int k = 0; k < M; k++) JH_TRY(pass[k].normal(t[k].y, xs[k]));
-        JH_TRY(allreduce([&](int k) { return t[k].y; }));
+        for (int k = 0; k < M; k++) JH_TRY(pass[k].normal(t[k][Y], xs[k]));
+        JH_TRY(allreduce(Y));
         double xb = 0.0, xax = 0.0, im = 0.0;
-        JH_TRY(jh_dot(xs[0], t[0].s, &xb, &im));
-        JH_TRY(jh_dot(xs[0], t[0].y, &xax, &im));
+        JH_TRY(jh_dot(xs[0], t[0][S], &xb, &im));
+        JH_TRY(jh_dot(xs[0], t[0][Y], &xax, &im));
         rr = s2 - 2.0 * xb + xax;
         if (damp != 0.0) {                                                // the functional CG decreases is ||r||^2 + damp^2 ||x||^2
             double x0n = 0.0;
@@ -1517,32 +1393,25 @@ static int cgnr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
             rr += damp * damp * x0n * x0n;
         }
         for (int k = 0; k < M; k++) {
-            JH_TRY(lincomb2(t[k].s, 1.0, t[k].s, -1.0, t[k].y));
-            if (damp != 0.0) JH_TRY(lincomb2(t[k].s, 1.0, t[k].s, -damp * damp, xs[k]));
+            JH_TRY(lincomb2(t[k][S], 1.0, t[k][S], -1.0, t[k][Y]));
+            if (damp != 0.0) JH_TRY(lincomb2(t[k][S], 1.0, t[k][S], -damp * damp, xs[k]));
         }
     }
     double nrm = 0.0;
-    JH_TRY(jh_norm(t[0].s, 2.0, &nrm));
+    JH_TRY(jh_norm(t[0][S], 2.0, &nrm));
     double gamma = nrm * nrm;
     const double gamma0 = gamma;
-    for (int k = 0; k < M; k++) JH_TRY(jh_copy(t[k].p, t[k].s));
+    for (int k = 0; k < M; k++) JH_TRY(jh_copy(t[k][P], t[k][S]));
     int itn = 0, istop = 0;
-    int64_t chunk = (n + 3) / 4;                                          // exchange ranges: 4, on 64 KiB boundaries (as lsqr_impl)
-    chunk = (chunk + 16383) / 16384 * 16384;
     // y = sum over the shards of A_k'A_k p.  Partitioned: in 4 element ranges -- the all-reduce of a finished range runs on the exchange
     // stream while the kernel of the next range computes; the library streams then wait for the exchange (no host synchronisation)
     auto normal_all = [&]() -> int {
-        if (ex == Exch::none) return pass[0].normal(t[0].y, t[0].p);
-        for (int64_t lo = 0; lo < n; lo += chunk) {
-            const int64_t cnt = lo + chunk < n ? chunk : n - lo;
-            for (int k = 0; k < M; k++) JH_TRY(jh_blockop_normal_mul_range(ops[k], t[k].y, t[k].p, lo, cnt));
-            if (ex == Exch::team) { JH_TRY(use(0)); JH_TRY(jh_comm_group_begin()); }
-            int st = JH_OK;
-            for (int k = 0; k < M && st == JH_OK; k++) st = jh_comm_allreduce_sum_range(t[k].y, lo, cnt);
-            if (ex == Exch::team) { (void)use(0); const int st2 = jh_comm_group_end(); if (st == JH_OK) st = st2; }
-            JH_TRY(st);
-        }
-        for (int k = 0; k < M; k++) { JH_TRY(use(k)); JH_TRY(jh_comm_join()); }
+        if (ex == Exch::none) return pass[0].normal(t[0][Y], t[0][P]);
+        JH_TRY(sh.for_ranges([&](int64_t lo, int64_t cnt) -> int {
+            for (int k = 0; k < M; k++) JH_TRY(jh_blockop_normal_mul_range(ops[k], t[k][Y], t[k][P], lo, cnt));
+            return sh.grouped([&](int k) { return jh_comm_allreduce_sum_range(t[k][Y], lo, cnt); });
+        }));
+        for (int k = 0; k < M; k++) { JH_TRY(sh.use(k)); JH_TRY(jh_comm_join()); }
         return JH_OK;
     };
     if (gamma > 0) {
@@ -1550,9 +1419,9 @@ static int cgnr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
             itn++;
             JH_TRY(normal_all());                                         // the ONE pass over the operator
             if (damp != 0.0)
-                for (int k = 0; k < M; k++) JH_TRY(lincomb2(t[k].y, 1.0, t[k].y, damp * damp, t[k].p));
+                for (int k = 0; k < M; k++) JH_TRY(lincomb2(t[k][Y], 1.0, t[k][Y], damp * damp, t[k][P]));
             double delta = 0.0, im = 0.0;
-            JH_TRY(jh_dot(t[0].p, t[0].y, &delta, &im));                  // replicas are identical: member 0 speaks for all
+            JH_TRY(jh_dot(t[0][P], t[0][Y], &delta, &im));                  // replicas are identical: member 0 speaks for all
             if (!(delta > 0) || !std::isfinite(delta)) {
                 istop = 6;
                 itn--;
@@ -1560,15 +1429,15 @@ static int cgnr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
             }
             const double alpha = gamma / delta;
             for (int k = 0; k < M; k++) {
-                JH_TRY(lincomb2(xs[k], 1.0, xs[k], alpha, t[k].p));      // x += alpha p
-                JH_TRY(lincomb2(t[k].s, 1.0, t[k].s, -alpha, t[k].y));   // s -= alpha (A'A + damp^2) p
+                JH_TRY(lincomb2(xs[k], 1.0, xs[k], alpha, t[k][P]));      // x += alpha p
+                JH_TRY(lincomb2(t[k][S], 1.0, t[k][S], -alpha, t[k][Y]));   // s -= alpha (A'A + damp^2) p
             }
             rr -= alpha * gamma;                                          // ||r||^2 (+ damp^2 ||x||^2 when damped: the functional's value)
             if (rr < 0) rr = 0;
-            JH_TRY(jh_norm(t[0].s, 2.0, &nrm));
+            JH_TRY(jh_norm(t[0][S], 2.0, &nrm));
             const double gamma_new = nrm * nrm;
             const double bk = gamma_new / gamma;
-            for (int k = 0; k < M; k++) JH_TRY(lincomb2(t[k].p, 1.0, t[k].s, bk, t[k].p));
+            for (int k = 0; k < M; k++) JH_TRY(lincomb2(t[k][P], 1.0, t[k][S], bk, t[k][P]));
             gamma = gamma_new;
             const double rnorm = std::sqrt(rr), arnorm = std::sqrt(gamma);
             if (history) { history[2 * (itn - 1)] = rnorm; history[2 * (itn - 1) + 1] = arnorm; }
@@ -1589,11 +1458,7 @@ static int cgnr_impl(const int M, const jh_blockop *const *ops, jh_bvec *const *
     res->acond = 0.0;
     res->arnorm = std::sqrt(gamma);
     res->xnorm = xnorm;
-    for (int k = 0; k < M; k++) {
-        jh_context *ck = jh_ctx_by_id(ops[k]->ctx);
-        if (ck) { JH_TRY(use(k)); JH_CHECK_HIP(hipStreamSynchronize(ck->stream)); }
-    }
-    return JH_OK;
+    return sh.sync_all();
 }
 
 extern "C" int jh_cgnr_solve(const jh_blockop *op, jh_bvec *b, jh_bvec *x, int use_x0, double damp, double atol, double btol, int maxiter,
@@ -1608,30 +1473,15 @@ extern "C" int jh_cgnr_solve(const jh_blockop *op, jh_bvec *b, jh_bvec *x, int u
 extern "C" int jh_cgnr_solve_partitioned(const jh_blockop *op, jh_bvec *b, jh_bvec *x, int use_x0, double damp, double atol, double btol,
                                          int maxiter, int force_maxiter, jh_lsqr_result *res, double *history)
 {
-    JH_TRY(jh_enter(op, b, x));
-    int nranks = 1, rank = 0, has_comm = 0;
-    (void)jh_comm_info(&nranks, &rank);
-    (void)jh_comm_exists(&has_comm);
-    if (has_comm == 2 && (nranks > 1 || jh_ctx().force_dist))
-        return jh_fail(JH_ERR_UNSUPPORTED, "jh_cgnr_solve_partitioned: this context is a member of a single-process team (jh_comm_init_all): "
-                       "jh_cgnr_solve_team takes all the members' shards in one call");
-    return cgnr_impl(1, &op, &b, &x, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history,
-                     (nranks > 1 || (has_comm && jh_ctx().force_dist)) ? Exch::ranks : Exch::none);
+    Exch ex = Exch::none;
+    JH_TRY(partitioned_exchange("jh_cgnr_solve", op, b, x, &ex));
+    return cgnr_impl(1, &op, &b, &x, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history, ex);
 }
 
 extern "C" int jh_cgnr_solve_team(int n, const jh_blockop *const *ops, jh_bvec *const *bs, jh_bvec *const *xs, int use_x0, double damp, double atol,
                                   double btol, int maxiter, int force_maxiter, jh_lsqr_result *res, double *history)
 {
-    JH_REQUIRE(n >= 1 && n <= JH_MAX_CTX && ops && bs && xs, "jh_cgnr_solve_team: need 1..%d members", JH_MAX_CTX);
-    for (int k = 0; k < n; k++) {
-        JH_REQUIRE(ops[k] && bs[k] && xs[k], "jh_cgnr_solve_team: null handle of member %d", k);
-        JH_TRY(jh_enter(ops[k], bs[k], xs[k]));
-        int nranks = 1, rank = 0, has_comm = 0;
-        (void)jh_comm_info(&nranks, &rank);
-        (void)jh_comm_exists(&has_comm);
-        JH_REQUIRE(has_comm == 2 && nranks == n && rank == k, "jh_cgnr_solve_team: the handles of member %d must live in member %d's context of a team of %d "
-                   "(jh_comm_init_all); found %s, rank %d of %d", k, k, n, has_comm == 2 ? "a team" : "no team", rank, nranks);
-    }
+    JH_TRY(team_members_ok("jh_cgnr_solve", n, ops, bs, xs));
     return cgnr_impl(n, ops, bs, xs, use_x0, damp, atol, btol, maxiter, force_maxiter, res, history, Exch::team);
 }
 
